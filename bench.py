@@ -13,10 +13,14 @@ resident in HBM before the timed region:
      --amp-dtype bf16: plain bf16, no scaling), fused 4-term
      region-adaptive loss on the labels of A, Adam step (N>1: DDP/RCCL gradient all-reduce overlapped with
      backward, SyncBN), EMA update.
-value = N * B * K / max-over-ranks(time of K steps)  [images/s].
+value = N * B * K / max-over-ranks(time of K steps)  [images/s];  ms_per_step = time of K steps / K.
 
-Prints ONE JSON line (contract in the task statement) with `roofline` (dominant hand-written kernel,
-timed live with HIP events on the launch stream) and `cpu_baseline` (the CPU oracle on the host cores).
+Prints ONE JSON line.  A plain run sets up, warms up, times the K steps (all alike) and prints the headline.
+--full adds what takes work of its own: the first timed step then runs every part in order on one stream with
+per-launch HIP events (`roofline`, `roofline_other`, `phases_ms`, the step_* fractions; part of `value`), and
+`cpu_baseline` (the CPU oracle on the host cores) runs after the timed region.
+--dump-outputs DIR writes what the last timed step computed (pseudo labels, loss terms, IAS thresholds, class
+sums, a fixed sample of the updated student / EMA-teacher weights) as DIR/<name>.npy, float32 / float64.
 """
 import argparse
 import json
@@ -70,7 +74,15 @@ def parse():
                         "whole GPU lease and return nothing; 0 = off")
     p.add_argument("--trainer", default="ConsistencySelfTrainingTrainer",
                    choices=["ConsistencySelfTrainingTrainer", "SelfTrainingTrainer"])
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also the figures beyond the headline: per-launch timing of the first timed step (roofline, phase "
+                        "split, step fractions; that step then runs serially on one stream) and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_cfg(world, trainer, amp_dtype="fp16"):
@@ -718,6 +730,43 @@ def cpu_baseline(cfg, size, threads, batch=2, reps=3):
                          info["cores_per_socket"], info["usable"])}
 
 
+DUMP_PARAM_SAMPLE = 1 << 20        # weights per model in the dumped sample (4 MiB as float32)
+DUMP_LABEL_MAX = 8 << 20           # pseudo-label pixels dumped whole up to this count (32 MiB), a seeded sample above
+
+
+def dump_outputs(out_dir, hp, losses, plbl):
+    """What the last timed step handed back, as <out_dir>/<name>.npy (float32 / float64, ~25 MB at batch 8): the pseudo-label
+    map, each loss term, the IAS thresholds and class sums it left behind, and the updated weights of the student (and EMA
+    teacher) at a fixed, seeded sample of positions over all parameters in registration order.  Two runs with the same
+    arguments write the same bits (seeded inputs and initial state, deterministic kernels; see main())."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a, dtype):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=dtype))
+
+    def sample(flat, n):
+        if flat.numel() <= n:
+            return flat.cpu().numpy()
+        g = torch.Generator(device="cpu").manual_seed(20240607)
+        idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+        return flat[idx.to(flat.device)].cpu().numpy()
+
+    def weight_sample(model):
+        return sample(torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]), DUMP_PARAM_SAMPLE)
+
+    save("pseudo_labels", plbl.cpu().numpy() if plbl.numel() <= DUMP_LABEL_MAX else sample(plbl.reshape(-1), DUMP_LABEL_MAX),
+         np.float32)
+    for k, v in losses.items():
+        save("loss_" + k, v.detach().double().cpu().numpy(), np.float64)
+    save("ias_thresholds", hp.thr, np.float64)
+    cnt, sfx = hp._stats
+    save("class_pixel_counts", cnt.cpu().numpy(), np.float64)
+    save("class_maxprob_sums_fx", sfx.cpu().numpy(), np.float64)
+    save("student_weights_sample", weight_sample(hp.model.module), np.float32)
+    if hp.teacher:
+        save("teacher_weights_sample", weight_sample(hp.ema), np.float32)
+
+
 class Watchdog:
     """A daemon THREAD of this rank (never a re-exec: the process has touched the GPU): `beat(stage)` after every finished
     stage / step; `limit` seconds without a beat -> every rank says on stderr where it stands (stage, step, collectives issued
@@ -835,6 +884,10 @@ def main():
     # HIAST_RESERVE_CUS=n (N > 1; HIAST_RESERVE_CUS_FORCE=1: also here): the main stream and every side stream leave n CUs alone
     cu_reserve = comm.apply_cu_reserve(world, device)
     torch.backends.cudnn.benchmark = bool(int(os.environ.get("HIAST_MIOPEN_FIND", "0")))
+    # the library convolutions left in the run (the fp32 training-mode forward that calibrates the synthetic state in
+    # HotPath._spread_head) pick deterministic algorithms: with the default ones that calibration, and every step after it,
+    # differed from run to run; the hand-written kernels of the step are deterministic on their own
+    torch.backends.cudnn.deterministic = True
 
     cfg = make_cfg(2 if args.rehearse_dist else world, args.trainer, args.amp_dtype)      # (gpu_num > 1 => SyncBN layers)
     import contextlib
@@ -844,7 +897,8 @@ def main():
         hp = HotPath(cfg, device, rank, world, args.batch, multi)   # must not precede the ONE JSON line on stdout
     dog.beat("model built")
     timer = KernelTimer()
-    timer.install()
+    if args.full:                       # (per-launch HIP events of the first timed step: the roofline figures)
+        timer.install()
 
     def sync():
         if multi:
@@ -857,8 +911,9 @@ def main():
         # whole-batch launches): the library's one-time algorithm search for those shapes stays out of the timed region,
         # and the caching allocator holds the whole-batch blocks that step asks for (with the serial step first and the
         # overlapped steps — half-batch blocks — after it, a timed run was seen to pay four fresh 537 MB device allocations,
-        # 5 ms each, inside the first timed step)
-        serial = it == args.warmup - 1 and args.warmup >= 2      # (a single warm-up step: the configuration of most timed steps)
+        # 5 ms each, inside the first timed step).  A plain run has no serial step: every warm-up step is like every timed one
+        serial = args.full and it == args.warmup - 1 and args.warmup >= 2     # (a single warm-up step: the configuration of
+                                                                               # most timed steps)
         hp.use_side = not serial
         HF.enable_wgrad_overlap(not serial)
         hp.step()
@@ -890,7 +945,6 @@ def main():
         K.confusion_hist(z, z, 2)
         torch.cuda.synchronize()
     marker()
-    timer.on = True
     from hiast_amd.utils import comm as _comm
     coll_before, coll_host_before = dict(_comm.COUNTS), dict(_comm.HOST_S)
     # phases are timed with HIP events on the launch stream: no host synchronisation inside the timed region (the only
@@ -899,13 +953,13 @@ def main():
     from hiast_amd import functional as HF
     t0 = time.perf_counter()
     for it in range(args.steps):
-        timer.on = it == 0              # per-launch events cost ~5 us each (460 per step): the first timed step only
+        timer.on = args.full and it == 0    # per-launch events cost ~5 us each (460 per step): the first timed step only
         hp.use_side = not timer.on      # ... and on those steps nothing runs beside the timed kernels (teacher forward,
         HF.enable_wgrad_overlap(not timer.on)   # pseudo-label forward and weight gradients on the main stream, one launch
                                                 # sequence per forward), so the per-launch durations are not stretched by
                                                 # co-running work
         e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-        last_losses, _ = hp.step(e)
+        last_losses, last_plbl = hp.step(e)
         marks.append(e)
         if not timer.on:
             host_parts.append([1e3 * (hp.host_marks[i + 1] - hp.host_marks[i]) for i in range(4)])
@@ -931,21 +985,23 @@ def main():
             collectives["gradient_buckets"] = int(hp.model._get_ddp_logging_data().get("num_buckets_reduced"))
         except Exception:
             pass
-    # phase split from the FIRST timed step only: it runs every part on the main stream (see above); in the other steps
-    # the pseudo-label forward runs beside the training forwards and the marks of the main stream do not separate them
-    ser = marks[:1]
-    if hp.pipelined:    # pseudo-label pass = [0,1] + [2,3]; training step = [1,2] + [3,4]
-        t_pl = sum(e[0].elapsed_time(e[1]) + e[2].elapsed_time(e[3]) for e in ser) * 1e-3 * args.steps
-        t_tr = sum(e[1].elapsed_time(e[2]) + e[3].elapsed_time(e[4]) for e in ser) * 1e-3 * args.steps
-    else:
-        t_pl = sum(e[0].elapsed_time(e[2]) for e in ser) * 1e-3 * args.steps
-        t_tr = sum(e[3].elapsed_time(e[4]) for e in ser) * 1e-3 * args.steps
+    # (--full) phase split from the FIRST timed step only: it runs every part on the main stream (see above); in the other
+    # steps the pseudo-label forward runs beside the training forwards and the marks of the main stream do not separate them
+    if args.full:
+        ser = marks[:1]
+        if hp.pipelined:    # pseudo-label pass = [0,1] + [2,3]; training step = [1,2] + [3,4]
+            t_pl = sum(e[0].elapsed_time(e[1]) + e[2].elapsed_time(e[3]) for e in ser) * 1e-3 * args.steps
+            t_tr = sum(e[1].elapsed_time(e[2]) + e[3].elapsed_time(e[4]) for e in ser) * 1e-3 * args.steps
+        else:
+            t_pl = sum(e[0].elapsed_time(e[2]) for e in ser) * 1e-3 * args.steps
+            t_tr = sum(e[3].elapsed_time(e[4]) for e in ser) * 1e-3 * args.steps
     timer.on = False
     marker()
     # unprofiled device-side gap at the step boundary: time between the event behind the last launch of step i (after the
     # EMA update / buffer copy) and the event in front of the first launch of step i + 1, on the main stream.  If the host
     # enqueues ahead of the device the two events complete back to back (~0); a host that arrives late shows as a gap.
-    gaps = [marks[i][4].elapsed_time(marks[i + 1][0]) for i in range(1, len(marks) - 1)]      # (step 0 is the serial one)
+    gaps = [marks[i][4].elapsed_time(marks[i + 1][0])                  # (--full: step 0 is the serial one)
+            for i in range(1 if args.full else 0, len(marks) - 1)]
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if multi:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -970,6 +1026,8 @@ def main():
         skipped = args.steps - (hp.opt.applied_steps() - applied_before)
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, hp, last_losses, last_plbl)
         imgs = world * args.batch * args.steps
         out = {
             "metric": "self-training images/sec (fwd+bwd+pseudo-label) at 1024x512",
@@ -994,9 +1052,7 @@ def main():
                        "batch_semantics": ("reference_bs%d: global batch split over the ranks + SyncBN (code/train.py:52-53)"
                                            % args.global_batch if args.global_batch else "per-GPU batch (weak scaling)"),
                        "parallelism": "dp1-rehearsal" if args.rehearse_dist else ("dp%d" % world if world > 1 else "single"), "cu_reserve": cu_reserve},
-            "phases_ms": {"pseudo_label": 1e3 * t_pl / args.steps, "train_step": 1e3 * t_tr / args.steps,
-                          "note": "of the first timed step, which runs every part in order on one stream (per-launch "
-                                  "events); the other steps overlap the parts on four streams"},
+            "full": args.full,
             # host time spent ENQUEUING each part (steps without per-launch events; the third entry includes the wait
             # for the histogram): the sum must stay below ms_per_step or the step is launch-bound
             "final_losses": final_losses, "ranks_agree": ranks_agree, "collectives_per_step": collectives,
@@ -1008,6 +1064,10 @@ def main():
                                         ["plabel_fwd_pass1", "hist_wait_thresholds_pass2", "-", "train_step"],
                                         [float(v) for v in np.mean(np.array(host_parts), axis=0)])) if host_parts else None,
         }
+        if args.full:
+            out["phases_ms"] = {"pseudo_label": 1e3 * t_pl / args.steps, "train_step": 1e3 * t_tr / args.steps,
+                                "note": "of the first timed step, which runs every part in order on one stream (per-launch "
+                                        "events); the other steps overlap the parts on four streams"}
         groups = timer.summary()
         groups_all = list(groups)
         if groups:
@@ -1022,8 +1082,9 @@ def main():
                                                             "frac_algorithmic_vs_dense", "traffic", "traffic_source",
                                                             "avg_launch_ms", "launches_per_step", "note") if kk in o}
                                      for o in others]
-        out.update(step_fractions(groups_all, 1e3 * elapsed / args.steps, 1e3 * (t_pl + t_tr) / args.steps))
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out.update(step_fractions(groups_all, 1e3 * elapsed / args.steps, 1e3 * (t_pl + t_tr) / args.steps))
+        if args.full and not args.no_cpu_baseline and world == 1:
             dog.stop()          # (the CPU baseline reports its own progress on stderr)
             try:
                 with contextlib.redirect_stdout(sys.stderr):

@@ -361,6 +361,49 @@ def test_bench_steps_run_on_finite_data():
         assert bool(torch.isfinite(p).all())
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the headline line only (no per-launch figures, no CPU baseline), and the
+    last timed step's outputs as float32 / float64 .npy files within 64 MB, pseudo labels shaped like the batch — the same
+    bits in a second run with the same arguments"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+
+    def run(out_dir):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "2", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600,
+                           env=env, cwd=root)
+        assert p.returncode == 0, (p.returncode, p.stderr[-4000:])
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, p.stdout[-2000:]
+        return json.loads(lines[0])
+
+    out_dir = tmp_path / "dump"
+    d = run(out_dir)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["unit"] == "images/s" and d["dtype"] == "fp16"
+    assert d["value"] > 0 and abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3e-3)) <= 1e-6 * d["value"]
+    for k in ("roofline", "phases_ms", "cpu_baseline", "step_frac_mfma_issued"):
+        assert k not in d, k
+    files = {f.name[:-4]: np.load(str(f)) for f in out_dir.iterdir()}
+    assert {"pseudo_labels", "ias_thresholds", "class_pixel_counts", "class_maxprob_sums_fx", "student_weights_sample",
+            "teacher_weights_sample"} <= set(files)
+    assert {"loss_" + k for k in d["final_losses"]} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["pseudo_labels"].shape == (2, 512, 1024) and files["ias_thresholds"].shape == (C,)
+    assert all(np.isfinite(a).all() for a in files.values())
+    for k, v in d["final_losses"].items():
+        assert abs(float(files["loss_" + k].mean()) - v) <= 1e-6 * max(1.0, abs(v)), k
+    again = tmp_path / "dump2"
+    assert run(again)["final_losses"] == d["final_losses"]
+    for name, a in files.items():
+        b = np.load(str(again / (name + ".npy")))
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), name
+
+
 def _sharded_gen_worker(rank, world_size, port, cfg_dict, save_dir, batch, backend="gloo", split="2"):
     import sys
     import torch.distributed as dist

@@ -216,8 +216,10 @@ def test_deeplab_vs_reference(golden):
         x = torch.from_numpy(synth.normal_f32(900 + ord(tag), (1, 3, H, W)))
         with torch.no_grad():
             pred, feat = deeplab_ref.deeplab_v2(x, sd)
-        assert np.allclose(pred.numpy(), g["pred_" + tag], rtol=1e-4, atol=1e-4)
-        assert np.allclose(feat.numpy()[:, ::64], g["feat_sub_" + tag], rtol=1e-4, atol=1e-4)
+        # atol at the scale of the map: its entries reach 1e6, small ones are differences of such terms, and the CPU's
+        # float32 summation order (it differs between CPU models) moves them by a few ulps of the largest values
+        for got, want in ((pred.numpy(), g["pred_" + tag]), (feat.numpy()[:, ::64], g["feat_sub_" + tag])):
+            assert np.allclose(got, want, rtol=1e-4, atol=1e-5 * np.abs(want).max())
     x = torch.from_numpy(synth.normal_f32(950, (2, 3, 65, 129)))
     with torch.no_grad():
         pred, _ = deeplab_ref.deeplab_v2(x, sd, train=True)
