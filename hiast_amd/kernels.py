@@ -626,6 +626,133 @@ def multi_copy(plan):
     check(_lib.load().hiast_multi_copy(_ptr(plan.table), plan.n, _stream()), "hiast_multi_copy")
 
 
+# ------------------------------------------------------------------------------- K15 device-side sample path
+AUG_REC_WORDS, AUG_MAX_OPS = 20, 8
+AUG_OPS_WORDS = 4 + 2 * AUG_MAX_OPS
+
+
+def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
+    """host-side bounds of a batch's record tables (numpy views of the HOST tensors): every offset + extent inside its
+    blob, every table index inside the sample's window — a kernel that reads outside can take the node down"""
+    def inside(off, n, size, what, b):
+        if off < 0 or off % 4 != 0 or off + n > size:
+            raise ValueError("device_aug: sample %d: %s [%d, +%d) outside its blob of %d" % (b, what, off, n, size))
+    B, V = recs.shape[0], ops.shape[0]
+    if recs.shape != (B, AUG_REC_WORDS) or ops.shape != (V, B, AUG_OPS_WORDS) or V < 1:
+        raise ValueError("device_aug: record tables of shape %s / %s" % (recs.shape, ops.shape))
+    for b in range(B):
+        r = [int(v) for v in recs[b]]
+        kind = r[0]
+        if kind == 1:
+            inside(r[2], oh * ow, blob_n, "finished label", b)
+            for k in range(V):
+                if int(ops[k, b, 0]) != 1:
+                    raise ValueError("device_aug: sample %d: view %d of a finished sample has kind %d" % (b, k, int(ops[k, b, 0])))
+                inside(int(ops[k, b, 1]), oh * ow * 3, blob_n, "finished view %d" % k, b)
+            continue
+        if kind != 0:
+            raise ValueError("device_aug: sample %d: record kind %d" % (b, kind))
+        ch, cw = r[6], r[7]
+        if not (0 < ch <= max_ch and cw > 0):
+            raise ValueError("device_aug: sample %d: window %dx%d (max_ch %d)" % (b, ch, cw, max_ch))
+        inside(r[1], ch * cw * 3, blob_n, "image", b)
+        inside(r[2], ch * cw, blob_n, "label", b)
+        if r[3] >= 0 or r[4] >= 0 or r[5] >= 0:
+            inside(r[3], ch * cw * 3, blob_n, "paste image", b)
+            inside(r[4], ch * cw, blob_n, "paste label", b)
+            inside(r[5], 256, blob_n, "paste table", b)
+        for (lo, n, k, taps, n_out, n_in, nm) in ((r[9], r[10], r[11], r[12], ow, cw, "horizontal"),
+                                                  (r[13], r[14], r[15], r[16], oh, ch, "vertical")):
+            if taps < 1:
+                raise ValueError("device_aug: sample %d: %s tap count %d" % (b, nm, taps))
+            inside(lo, n_out, tabs.size, nm + " bounds", b)
+            inside(n, n_out, tabs.size, nm + " counts", b)
+            inside(k, n_out * taps, tabs.size, nm + " weights", b)
+            lo_v, n_v = tabs[lo:lo + n_out], tabs[n:n + n_out]
+            if lo_v.min() < 0 or n_v.min() < 0 or n_v.max() > taps or (lo_v + n_v).max() > n_in:
+                raise ValueError("device_aug: sample %d: %s table reads outside [0, %d)" % (b, nm, n_in))
+            if int(np.abs(tabs[k:k + n_out * taps].astype(np.int64)).reshape(n_out, taps).sum(1).max()) > (1 << 23) - 1:
+                raise ValueError("device_aug: sample %d: %s weights overflow the 32-bit accumulator" % (b, nm))
+        for (off, n_out, n_in, nm) in ((r[17], ow, cw, "nearest x"), (r[18], oh, ch, "nearest y")):
+            inside(off, n_out, tabs.size, nm, b)
+            v = tabs[off:off + n_out]
+            if v.min() < 0 or v.max() >= n_in:
+                raise ValueError("device_aug: sample %d: %s table reads outside [0, %d)" % (b, nm, n_in))
+        for k in range(V):
+            o = [int(v) for v in ops[k, b]]
+            if o[0] != 0 or not 0 <= o[2] <= AUG_MAX_OPS:
+                raise ValueError("device_aug: sample %d view %d: kind %d with %d ops" % (b, k, o[0], o[2]))
+            types = [o[4 + 2 * i] for i in range(o[2])]
+            if any(t not in (1, 2, 3) for t in types) or types.count(3) > 1:
+                raise ValueError("device_aug: sample %d view %d: op types %s" % (b, k, types))
+            for i, t in enumerate(types):
+                if t == 1:
+                    inside(o[5 + 2 * i], 256, blob_n, "view %d LUT %d" % (k, i), b)
+
+
+def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch):
+    """device tensors of one batch (blob uint8, tabs int32, recs int64 [B, 20]: include/hiast_hip.h, K15; ALREADY bounds-
+    checked by the caller) -> (uint8 [B, oh, ow, 3], uint8 label [B, oh, ow]): CopyPaste select, flip, crop, Pillow's
+    two-pass 8-bit resample and the nearest label gather, byte for byte"""
+    _req(blob, torch.uint8, 1, "blob")
+    _req(tabs, torch.int32, 1, "tabs")
+    _req(recs, torch.int64, 2, "recs")
+    B = recs.shape[0]
+    dev = blob.device
+    tmp = torch.empty((B, max_ch, ow, 3), dtype=torch.uint8, device=dev)
+    img = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=dev)
+    lbl = torch.empty((B, oh, ow), dtype=torch.uint8, device=dev)
+    check(_lib.load().hiast_aug_geometry_u8(_ptr(recs), _ptr(blob), _ptr(tabs), _ptr(tmp), _ptr(img), _ptr(lbl), B, max_ch,
+                                            oh, ow, _stream()), "hiast_aug_geometry_u8")
+    return img, lbl
+
+
+def aug_colour_u8(img_u8, ops, blob, equalize=True):
+    """one view's op rows (ops int64 [B, 20] on the device, bounds-checked by the caller) on uint8 [B, H, W, 3] -> a new
+    tensor.  equalize: some row holds an Equalize (its histogram + table launches are skipped otherwise)"""
+    _req(img_u8, torch.uint8, 4, "img_u8")
+    _req(ops, torch.int64, 2, "ops")
+    _req(blob, torch.uint8, 1, "blob")
+    B, H, W, three = img_u8.shape
+    assert three == 3 and tuple(ops.shape) == (B, AUG_OPS_WORDS)
+    lib = _lib.load()
+    eq = torch.empty((B, 3, 256), dtype=torch.uint8, device=img_u8.device)
+    if equalize:
+        hist = torch.empty((B, 3, 256), dtype=torch.int32, device=img_u8.device)
+        check(lib.hiast_aug_hist_u8(_ptr(ops), _ptr(blob), _ptr(img_u8), _ptr(hist), _ptr(eq), B, H * W, _stream()),
+              "hiast_aug_hist_u8")
+    out = torch.empty_like(img_u8)
+    check(lib.hiast_aug_colour_u8(_ptr(ops), _ptr(blob), _ptr(eq), _ptr(img_u8), _ptr(out), B, H * W, _stream()),
+          "hiast_aug_colour_u8")
+    return out
+
+
+def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
+    """HOST tensors of a collated device_aug batch (device_aug.build_batch_tables) -> ([uint8 [B, oh, ow, 3] per view],
+    uint8 label [B, oh, ow]) on `device`: four uploads, then geometry + one colour pass per view"""
+    for t, dt, nm in ((blob, torch.uint8, "blob"), (tabs, torch.int32, "tabs"), (recs, torch.int64, "recs"),
+                      (ops, torch.int64, "ops")):
+        if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError("aug_batch_u8: %s must be a contiguous host tensor of %s" % (nm, dt))
+    if torch.device(device).type != "cuda":
+        raise _lib.HiastLibraryError("the device-side sample path runs on the HIP device only")
+    recs_h, ops_h = recs.numpy(), ops.numpy()
+    _aug_check_tables(blob.numel(), tabs.numpy(), recs_h, ops_h, oh, ow, max_ch)
+    up = lambda t: (t if t.is_pinned() else t.pin_memory()).to(device, non_blocking=True)      # noqa: E731
+    blob_d, tabs_d, recs_d, ops_d = up(blob), up(tabs), up(recs), up(ops)
+    cur, lbl = aug_geometry_u8(blob_d, tabs_d, recs_d, oh, ow, max_ch)
+    views = []
+    for k in range(ops_h.shape[0]):
+        planned = ops_h[k, :, 0] == 0
+        has_ops = bool((ops_h[k, planned, 2] > 0).any())
+        if has_ops or (k > 0 and not planned.all()):       # (finished samples: view k is copied in from the blob)
+            n = ops_h[k, :, 2]
+            eq = bool(((ops_h[k][:, 4::2] == 3) & (np.arange(AUG_MAX_OPS)[None, :] < n[:, None]) & planned[:, None]).any())
+            cur = aug_colour_u8(cur, ops_d[k], blob_d, equalize=eq)
+        views.append(cur)
+    return views, lbl
+
+
 # ------------------------------------------------------------------------------- K13 Adam
 class AdamPlan:
     """chunk tables for one list of parameter sizes (static); the pointer / lr records are rebuilt per step because

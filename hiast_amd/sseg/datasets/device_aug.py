@@ -1,0 +1,505 @@
+"""Device-side sample path (cfg.dataset.device_aug / HIAST_DEVICE_AUG=1): a sample is split into a PLAN — every random
+decision of augmentations.aug(), drawn on the host in the same order from the same `random` / `np.random.RandomState`
+streams, image-independent — and an EXECUTION, a pure function of bytes + plan.  DataLoader workers keep decoding and
+drawing; resampling and recolouring run on the device (hiast_amd/csrc/sample_aug.hip), byte-identical to the host code.
+
+    plan_sample(aug_fun, in_shape, index)     -> list of view plans (one per entry of a multi-view aug list)
+    execute_plan_host(plan, img, lbl)         -> what augmentations.aug() returns, computed from the plan in numpy: the
+                                                 definition the kernels are tested against
+    pack_sample / collate                     -> what a worker hands over: ONE uint8 blob, ONE int32 table blob and one
+                                                 record row per sample (offsets, not pointers: built without a device)
+    assemble_device_batch(batch, device)      -> what utils.to_device_batch returns (normalised float32 CHW views, labels)
+
+A view plan is {"ops": [...], "host": bool}; ops are ("geom", Geometry), ("lut", uint8[256]), ("gray",), ("equalize",)
+and ("host", name).  ColorJitter, GaussianBlur and FDA have no device form (PIL's C HSV conversion, scipy's float64
+correlate, an FFT): a sample whose plan holds one of them is run through augmentations.aug() by the worker as before
+and handed over as finished uint8 views (`needs_host`).
+
+Resampling restates Pillow's two-pass 8-bit resample in integers (ImagingResample: per-axis coefficient tables in
+float64, rounded to 22-bit fixed point, horizontal pass rounded to uint8, then the vertical pass) and its affine
+nearest-neighbour scaler (a running float64 sum per axis)."""
+import random
+
+import numpy as np
+import torch
+
+from hiast_amd.sseg.datasets import augmentations as A
+
+PRECISION_BITS = 22          # Pillow: 32 - 8 - 2
+MAX_OPS = 8                  # colour ops per view the device record holds (after composing neighbouring LUTs)
+HOST_ONLY = (A.ColorJitter, A.GaussianBlur, A.FDA)
+
+OP_LUT, OP_GRAY, OP_EQUALIZE = 1, 2, 3
+
+
+# ------------------------------------------------------------------------------------------------- tables
+def bilinear_table(n_in, n_out):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the bilinear (triangle) filter over a whole axis:
+    -> (lo int32[n_out], n int32[n_out], k int32[n_out, taps]); taps beyond n are 0.  n_in == n_out has no pass in
+    Pillow: the identity table (one tap of weight 2^P) reproduces that exactly."""
+    one = 1 << PRECISION_BITS
+    if n_in == n_out:
+        return (np.arange(n_out, dtype=np.int32), np.ones(n_out, np.int32), np.full((n_out, 1), one, np.int32))
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ss = 1.0 / fs
+    taps = int(np.ceil(support)) * 2 + 1
+    lo = np.zeros(n_out, np.int32)
+    n = np.zeros(n_out, np.int32)
+    k = np.zeros((n_out, taps), np.int32)
+    for i in range(n_out):
+        c = (i + 0.5) * scale
+        x0 = max(int(c - support + 0.5), 0)
+        x1 = min(int(c + support + 0.5), n_in)
+        w = [max(0.0, 1.0 - abs((j + x0 - c + 0.5) * ss)) for j in range(x1 - x0)]
+        tot = 0.0
+        for v in w:
+            tot += v
+        lo[i], n[i] = x0, x1 - x0
+        for j, v in enumerate(w):
+            if tot != 0.0:
+                v = v / tot
+            k[i, j] = int(0.5 + v * one)
+    return lo, n, k
+
+
+def nearest_table(n_in, n_out):
+    """Pillow's ImagingScaleAffine: the source index of every output index, from the running float64 sum"""
+    a = n_in / n_out
+    x = 0.5 * a
+    tab = np.zeros(n_out, np.int32)
+    for i in range(n_out):
+        tab[i] = min(int(x), n_in - 1)
+        x += a
+    return tab
+
+
+class Geometry:
+    """flip + crop window + resize (+ a crop of the resized frame) of one source frame as tables over the bytes a worker
+    hands over: `src` = (y1, y2, x1, x2), the slice of the UNFLIPPED source frame; with `flip` its columns are read right
+    to left.  All table indices are relative to that (flipped) slice."""
+
+    def __init__(self, src, flip, out, hlo, hn, hk, vlo, vn, vk, nx, ny):
+        self.src, self.flip, self.out = tuple(int(v) for v in src), bool(flip), (int(out[0]), int(out[1]))
+        self.hlo, self.hn, self.hk, self.vlo, self.vn, self.vk, self.nx, self.ny = hlo, hn, hk, vlo, vn, vk, nx, ny
+
+
+class _GeomState:
+    """the geometric transforms met so far on the way down one chain: out = crop_out(resize(crop(flip?(frame))))"""
+
+    def __init__(self, shape):
+        self.H, self.W = int(shape[0]), int(shape[1])
+        self.flip = False
+        self.win = (0, self.H, 0, self.W)        # in the coordinates of the (flipped) frame
+        self.resize = None
+        self.out_win = None
+        self.touched = False
+
+    def shape(self):
+        if self.out_win is not None:
+            return self.out_win[1] - self.out_win[0], self.out_win[3] - self.out_win[2]
+        if self.resize is not None:
+            return self.resize
+        return self.win[1] - self.win[0], self.win[3] - self.win[2]
+
+    def do_flip(self):
+        if self.resize is not None:
+            return False
+        y1, y2, x1, x2 = self.win                # flip of a window = the mirrored window of the flipped frame
+        self.win = (y1, y2, self.W - x2, self.W - x1)
+        self.flip = not self.flip
+        self.touched = True
+        return True
+
+    def do_crop(self, y1, y2, x1, x2):
+        self.touched = True
+        if self.resize is None:
+            oy, ox = self.win[0], self.win[2]
+            self.win = (oy + y1, oy + y2, ox + x1, ox + x2)
+        else:
+            oy, ox = (self.out_win[0], self.out_win[2]) if self.out_win is not None else (0, 0)
+            self.out_win = (oy + y1, oy + y2, ox + x1, ox + x2)
+        return True
+
+    def do_resize(self, h, w):
+        if self.shape() == (h, w):               # Resize.apply / Image.resize to the same size: the bytes unchanged
+            return True
+        if self.resize is not None:
+            return False
+        self.resize = (int(h), int(w))
+        self.touched = True
+        return True
+
+    def build(self):
+        y1, y2, x1, x2 = self.win
+        ch, cw = y2 - y1, x2 - x1
+        rh, rw = self.resize if self.resize is not None else (ch, cw)
+        hlo, hn, hk = bilinear_table(cw, rw)
+        vlo, vn, vk = bilinear_table(ch, rh)
+        nx, ny = nearest_table(cw, rw), nearest_table(ch, rh)
+        if self.out_win is not None:
+            oy1, oy2, ox1, ox2 = self.out_win
+            hlo, hn, hk, nx = hlo[ox1:ox2], hn[ox1:ox2], hk[ox1:ox2], nx[ox1:ox2]
+            vlo, vn, vk, ny = vlo[oy1:oy2], vn[oy1:oy2], vk[oy1:oy2], ny[oy1:oy2]
+        # hand over only the rows / columns a table reads
+        xa = int(min(hlo.min(), nx.min()))
+        xb = int(max((hlo + hn).max(), nx.max() + 1))
+        ya = int(min(vlo.min(), ny.min()))
+        yb = int(max((vlo + vn).max(), ny.max() + 1))
+        hlo, nx, vlo, ny = hlo - xa, nx - xa, vlo - ya, ny - ya
+        fx1, fx2 = x1 + xa, x1 + xb              # columns of the (flipped) frame
+        sx1, sx2 = (self.W - fx2, self.W - fx1) if self.flip else (fx1, fx2)
+        c = np.ascontiguousarray
+        return Geometry((y1 + ya, y1 + yb, sx1, sx2), self.flip, (len(vlo), len(hlo)),
+                        c(hlo, np.int32), c(hn, np.int32), c(hk, np.int32), c(vlo, np.int32), c(vn, np.int32),
+                        c(vk, np.int32), c(nx, np.int32), c(ny, np.int32))
+
+
+# ------------------------------------------------------------------------------------------------- plan
+def _lut_of(t, params):
+    """the 256-entry table the host transform applies; None = the bytes unchanged"""
+    if isinstance(t, A.RandomContrast):
+        return A._brightness_contrast_lut(params["alpha"], 0.0)
+    if isinstance(t, A.RandomBrightness):
+        return A._brightness_contrast_lut(1.0, params["beta"])
+    if isinstance(t, A.Posterize):
+        bits = params["bits"]
+        if bits == 0:
+            return np.zeros(256, np.uint8)
+        if bits == 8:
+            return None
+        return np.arange(256, dtype=np.uint8) & np.uint8(~np.uint8(2 ** (8 - bits) - 1))
+    if isinstance(t, A.Solarize):
+        thr = params["threshold"]
+        return np.array([i if i < thr else 255 - i for i in range(256)], np.uint8)
+    raise TypeError(type(t).__name__)
+
+
+class _Walker:
+    """one chain of views: the walk of augmentations.aug() with its draws, recording instead of touching pixels"""
+
+    def __init__(self, in_shape):
+        self.geom = _GeomState(in_shape)
+        self.geom_open = True                    # no pixel op recorded yet: geometry may still be folded into view 0's op
+        self.ops = []
+        self.host = False
+        self.stop = False                        # FDA: its params() read the image — the draws cannot be finished here
+
+    def begin_view(self):
+        self.ops = []
+
+    def end_view(self):
+        self._close_geometry()
+        return {"ops": self.ops, "host": any(o[0] == "host" for o in self.ops)}
+
+    def _close_geometry(self):
+        if self.geom_open:
+            self.ops.insert(0, ("geom", self.geom.build()))
+            self.geom_open = False
+
+    def _pixel_op(self, op):
+        self._close_geometry()
+        if op[0] == "lut" and self.ops and self.ops[-1][0] == "lut":
+            self.ops[-1] = ("lut", op[1][self.ops[-1][1]])          # lut2[lut1]: the same bytes in one pass
+        else:
+            self.ops.append(op)
+
+    def _geom_op(self, ok):
+        if not (self.geom_open and ok):          # geometry after a pixel op, or a second resize: no device form
+            self._close_geometry()
+            self.ops.append(("host", "geometry"))
+
+    def walk(self, t):
+        if self.stop:
+            return
+        if isinstance(t, A.SomeOf):
+            if random.random() < t.p:
+                rs = np.random.RandomState(random.randint(0, 2 ** 32 - 1))
+                for i in rs.choice(len(t.transforms), size=t.n, replace=t.replace):
+                    self.walk(t.transforms[int(i)])
+            return
+        if isinstance(t, A.Compose):
+            if random.random() < t.p:
+                for c in t.transforms:
+                    self.walk(c)
+            return
+        if isinstance(t, A.FDA):
+            self._pixel_op(("host", "FDA"))
+            self.stop = True
+            return
+        if not random.random() < t.p:
+            return
+        params = t.params(None)
+        g = self.geom
+        if isinstance(t, A.HorizontalFlip):
+            self._geom_op(self.geom_open and g.do_flip())
+        elif isinstance(t, A.Resize):
+            self._geom_op(self.geom_open and g.do_resize(t.h, t.w))
+        elif isinstance(t, A.RandomSizedCrop):
+            H, W = g.shape()
+            ch, cw = min(params["ch"], H), min(params["cw"], W)
+            win = A._crop_coords(H, W, ch, cw, params["h_start"], params["w_start"])
+            self._geom_op(self.geom_open and g.do_crop(*win) and g.do_resize(t.h, t.w))
+        elif isinstance(t, A.RandomCrop):
+            H, W = g.shape()
+            if t.h > H or t.w > W:
+                raise ValueError("RandomCrop: crop %dx%d is larger than the image %dx%d" % (t.h, t.w, H, W))
+            self._geom_op(self.geom_open and g.do_crop(*A._crop_coords(H, W, t.h, t.w, params["h_start"], params["w_start"])))
+        elif isinstance(t, HOST_ONLY):
+            self._pixel_op(("host", type(t).__name__))
+        elif isinstance(t, (A.RandomContrast, A.RandomBrightness, A.Posterize, A.Solarize)):
+            lut = _lut_of(t, params)
+            if lut is not None:
+                self._pixel_op(("lut", np.asarray(lut, np.uint8)))
+        elif isinstance(t, A.ToGray):
+            self._pixel_op(("gray",))
+        elif isinstance(t, A.Equalize):
+            self._pixel_op(("equalize",))
+        else:
+            self._pixel_op(("host", type(t).__name__))
+
+
+def plan_sample(aug_fun, in_shape, index=None):
+    """-> list of view plans (one per view; a single aug gives a list of one).  Consumes exactly the draws
+    augmentations.aug(aug_fun, img, lbl, index) consumes unless the plan `needs_host` through an FDA, whose parameters read
+    the image: the caller restores the state it saved and runs aug() (see BaseDataset)."""
+    if index is not None:
+        random.seed(index)
+    w = _Walker(in_shape)
+    views = []
+    for f in (aug_fun if isinstance(aug_fun, (list, tuple)) else [aug_fun]):
+        w.begin_view()
+        if f is not None:
+            w.walk(f)
+        views.append(w.end_view())
+    for v in views:        # what the device records hold: bounded op lists, at most one Equalize per view
+        n_eq = sum(1 for o in v["ops"] if o[0] == "equalize")
+        if n_eq > 1 or sum(1 for o in v["ops"] if o[0] != "geom") > MAX_OPS:
+            v["host"] = True
+    return views
+
+
+def needs_host(plan):
+    return any(v["host"] for v in plan)
+
+
+def plan_window(plan):
+    """(y1, y2, x1, x2) of the source frame the plan reads"""
+    return plan[0]["ops"][0][1].src
+
+
+# ------------------------------------------------------------------------------------------------- host executor
+def _resample_axis1(a, lo, n, k):
+    """a [R, n_in, C] uint8 -> [R, n_out, C] uint8: one integer pass of Pillow's 8-bit resample along axis 1"""
+    acc = np.full((a.shape[0], len(lo), a.shape[2]), 1 << (PRECISION_BITS - 1), np.int32)
+    for t in range(k.shape[1]):
+        live = n > t
+        if not live.any():
+            break
+        idx = np.minimum(lo + t, a.shape[1] - 1)
+        acc += np.where(live, k[:, t], 0).astype(np.int32)[None, :, None] * a[:, idx].astype(np.int32)
+    return np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
+
+
+def equalize_luts(img):
+    """per channel the table augmentations._equalize_cv_channel applies (a constant channel keeps its value)"""
+    luts = np.zeros((img.shape[2], 256), np.uint8)
+    for c in range(img.shape[2]):
+        hist = np.bincount(img[..., c].ravel(), minlength=256)
+        first = int(np.nonzero(hist)[0][0])
+        total = int(img[..., c].size)
+        if hist[first] == total:
+            luts[c, :] = first
+            continue
+        scale = 255.0 / (total - hist[first])
+        s = 0
+        for i in range(first + 1, 256):
+            s += int(hist[i])
+            luts[c, i] = min(255, max(0, int(round(s * scale))))
+    return luts
+
+
+def execute_geometry_host(g, raw_img, raw_lbl, paste=None):
+    """raw_img / raw_lbl: the slices g.src of the frame; paste = (src_img, src_lbl, table uint8[256]) over the same
+    slice: the CopyPaste composite, taken per pixel before resampling"""
+    if paste is not None:
+        p_img, p_lbl, table = paste
+        sel = np.asarray(table, np.uint8)[p_lbl] != 0
+        raw_img = np.where(sel[..., None], p_img, raw_img)
+        raw_lbl = np.where(sel, p_lbl, raw_lbl)
+    if g.flip:
+        raw_img, raw_lbl = raw_img[:, ::-1], raw_lbl[:, ::-1]
+    h8 = _resample_axis1(raw_img, g.hlo, g.hn, g.hk)
+    out = _resample_axis1(h8.transpose(1, 0, 2), g.vlo, g.vn, g.vk).transpose(1, 0, 2)
+    return np.ascontiguousarray(out), np.ascontiguousarray(raw_lbl[g.ny][:, g.nx])
+
+
+def execute_colour_host(ops, img):
+    for op in ops:
+        if op[0] == "lut":
+            img = op[1][img]
+        elif op[0] == "gray":
+            img = np.repeat(A._gray_cv(img)[..., None], 3, axis=2)
+        elif op[0] == "equalize":
+            luts = equalize_luts(img)
+            img = np.stack([luts[c][img[..., c]] for c in range(img.shape[2])], axis=2)
+        else:
+            raise ValueError("op %r has no plan form (host fallback)" % (op[0],))
+    return img
+
+
+def execute_plan_host(plan, img, lbl, paste=None, sliced=False):
+    """numpy execution of a plan: -> ([image per view], [label per view]), always lists (augmentations.aug() returns a bare
+    image / label for a single aug).  img / lbl: the source frame, or with `sliced` the slices plan_window(plan) of it
+    (what a worker hands over); paste = (source image, source label, table) of CopyPaste.run_plan, sliced likewise."""
+    g = plan[0]["ops"][0][1]
+    if not sliced:
+        y1, y2, x1, x2 = g.src
+        img, lbl = img[y1:y2, x1:x2], lbl[y1:y2, x1:x2]
+        if paste is not None:
+            paste = (paste[0][y1:y2, x1:x2], paste[1][y1:y2, x1:x2], paste[2])
+    cur, label = execute_geometry_host(g, img, lbl, paste)
+    imgs, lbls = [], []
+    for k, v in enumerate(plan):
+        cur = execute_colour_host(v["ops"][1:] if k == 0 else v["ops"], cur)
+        imgs.append(cur)
+        lbls.append(label)
+    return imgs, lbls
+
+
+# ------------------------------------------------------------------------------------------------- hand-over
+# one int64 record row per sample (offsets into the batch's uint8 blob / int32 table blob)
+R_KIND, R_IMG, R_LBL, R_PIMG, R_PLBL, R_PTAB, R_CH, R_CW, R_FLIP, R_HLO, R_HN, R_HK, R_HT, R_VLO, R_VN, R_VK, R_VT, R_NX, \
+    R_NY = range(19)
+REC_WORDS = 20
+# per (view, sample): kind, offset of the finished view, n ops, then (type, blob offset of the table) x MAX_OPS
+OPS_WORDS = 4 + 2 * MAX_OPS
+KIND_PLAN, KIND_FINISHED = 0, 1
+
+
+def _align(n, a=16):
+    return (n + a - 1) // a * a
+
+
+class _Blob:
+    def __init__(self, dtype):
+        self.parts, self.size, self.dtype = [], 0, dtype
+
+    def add(self, a):
+        a = np.ascontiguousarray(a, self.dtype).reshape(-1)
+        off = self.size
+        self.parts.append((off, a))
+        self.size = _align(off + a.size, 16)
+        return off
+
+    def join(self):
+        out = np.zeros(max(self.size, 16), self.dtype)
+        for off, a in self.parts:
+            out[off:off + a.size] = a
+        return out
+
+
+def pack_sample(plan, raw_img, raw_lbl, paste=None):
+    """what a worker returns for a planned sample: {"plan", "raw"} with the slices of plan_window(plan)"""
+    raw = {"img": torch.from_numpy(np.ascontiguousarray(raw_img)), "lbl": torch.from_numpy(np.ascontiguousarray(raw_lbl))}
+    if paste is not None:
+        raw["paste_img"] = torch.from_numpy(np.ascontiguousarray(paste[0]))
+        raw["paste_lbl"] = torch.from_numpy(np.ascontiguousarray(paste[1]))
+        raw["paste_table"] = torch.from_numpy(np.ascontiguousarray(paste[2], np.uint8))
+    return {"raw": raw, "plan": plan}
+
+
+def pack_finished(imgs, lbls):
+    """a host-fallback sample: finished uint8 views (lists for multi-view) as utils.transform(raw_u8=True) returns them"""
+    multi = isinstance(imgs, (list, tuple))
+    return {"raw": {"views": list(imgs) if multi else [imgs], "lbl": lbls[0] if multi else lbls}, "plan": None,
+            "multi": multi}
+
+
+def build_batch_tables(samples):
+    """samples: the {"raw", "plan"} parts of a batch -> dict of tensors: blob uint8, tabs int32, recs int64 [B, REC_WORDS],
+    ops int64 [V, B, OPS_WORDS], meta int64 [n_views, out_h, out_w, max_ch, multi]"""
+    B = len(samples)
+    blob, tabs = _Blob(np.uint8), _Blob(np.int32)
+    recs = np.full((B, REC_WORDS), -1, np.int64)
+    out, n_views, multi = None, None, None
+    for s in samples:
+        if s["plan"] is None:
+            v, shp, m = len(s["raw"]["views"]), tuple(s["raw"]["lbl"].shape), s["multi"]
+        else:
+            v, shp, m = len(s["plan"]), s["plan"][0]["ops"][0][1].out, len(s["plan"]) > 1
+        if out is None:
+            out, n_views, multi = shp, v, m
+        if (shp, v) != (out, n_views):
+            raise ValueError("device_aug batch: samples of different output size / view count (%s x%d vs %s x%d)"
+                             % (shp, v, out, n_views))
+    ops = np.zeros((n_views, B, OPS_WORDS), np.int64)
+    max_ch = 1
+    for b, s in enumerate(samples):
+        raw, r = s["raw"], recs[b]
+        if s["plan"] is None:
+            r[R_KIND] = KIND_FINISHED
+            r[R_LBL] = blob.add(raw["lbl"].numpy())
+            for k, v in enumerate(raw["views"]):
+                ops[k, b, 0], ops[k, b, 1] = KIND_FINISHED, blob.add(v.numpy())
+            r[R_IMG] = ops[0, b, 1]
+            continue
+        g = s["plan"][0]["ops"][0][1]
+        ch, cw = g.src[1] - g.src[0], g.src[3] - g.src[2]
+        if tuple(raw["img"].shape) != (ch, cw, 3) or tuple(raw["lbl"].shape) != (ch, cw):
+            raise ValueError("device_aug: raw slices %s do not match the plan's window %s" % (tuple(raw["img"].shape), g.src))
+        r[R_KIND], r[R_CH], r[R_CW], r[R_FLIP] = KIND_PLAN, ch, cw, int(g.flip)
+        r[R_IMG], r[R_LBL] = blob.add(raw["img"].numpy()), blob.add(raw["lbl"].numpy())
+        if "paste_img" in raw:
+            r[R_PIMG], r[R_PLBL] = blob.add(raw["paste_img"].numpy()), blob.add(raw["paste_lbl"].numpy())
+            r[R_PTAB] = blob.add(raw["paste_table"].numpy())
+        r[R_HLO], r[R_HN], r[R_HK], r[R_HT] = tabs.add(g.hlo), tabs.add(g.hn), tabs.add(g.hk), g.hk.shape[1]
+        r[R_VLO], r[R_VN], r[R_VK], r[R_VT] = tabs.add(g.vlo), tabs.add(g.vn), tabs.add(g.vk), g.vk.shape[1]
+        r[R_NX], r[R_NY] = tabs.add(g.nx), tabs.add(g.ny)
+        max_ch = max(max_ch, ch)
+        for k, v in enumerate(s["plan"]):
+            row = ops[k, b]
+            row[0] = KIND_PLAN
+            for op in (v["ops"][1:] if k == 0 else v["ops"]):
+                i = int(row[2])
+                if op[0] == "lut":
+                    row[4 + 2 * i], row[5 + 2 * i] = OP_LUT, blob.add(op[1])
+                elif op[0] == "gray":
+                    row[4 + 2 * i] = OP_GRAY
+                elif op[0] == "equalize":
+                    row[4 + 2 * i] = OP_EQUALIZE
+                else:
+                    raise ValueError("op %r has no device form" % (op[0],))
+                row[2] = i + 1
+    return {"blob": torch.from_numpy(blob.join()), "tabs": torch.from_numpy(tabs.join()),
+            "recs": torch.from_numpy(recs), "ops": torch.from_numpy(ops),
+            "meta": torch.tensor([n_views, out[0], out[1], max_ch, int(multi)], dtype=torch.int64)}
+
+
+def collate(samples):
+    """DataLoader collate_fn of a device_aug dataset: the sample parts become ONE set of tables per batch (crop windows
+    differ in size, nothing is stacked); every other key collates as usual"""
+    from torch.utils.data import default_collate
+    rest = [{k: v for k, v in s.items() if k not in ("raw", "plan", "multi")} for s in samples]
+    out = default_collate(rest)
+    out["device_aug"] = build_batch_tables(samples)
+    return out
+
+
+def is_device_aug_batch(batch):
+    return isinstance(batch, dict) and "device_aug" in batch
+
+
+def assemble_device_batch(batch, device):
+    """a collated device_aug batch -> what utils.to_device_batch returns for the same samples: normalised float32 CHW
+    views (a list for a multi-view dataset) and uint8 labels (a list of the same tensor per view)"""
+    from hiast_amd import kernels as K
+    from hiast_amd.sseg.datasets.utils import MEAN, STD
+    t = batch["device_aug"]
+    n_views, oh, ow, max_ch, multi = (int(v) for v in t["meta"])
+    views, lbl = K.aug_batch_u8(t["blob"], t["tabs"], t["recs"], t["ops"], oh, ow, max_ch, device)
+    imgs = [K.normalize_u8(v, MEAN, STD) for v in views]
+    if multi:
+        return imgs, [lbl for _ in imgs]
+    return imgs[0], lbl

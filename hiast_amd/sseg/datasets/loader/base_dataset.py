@@ -10,7 +10,7 @@ import torch
 from PIL import Image
 from torch.utils.data import Dataset
 
-from hiast_amd.sseg.datasets import augmentations, utils
+from hiast_amd.sseg.datasets import augmentations, device_aug, utils
 
 
 class BaseDataset(Dataset):
@@ -66,14 +66,51 @@ class BaseDataset(Dataset):
             index = index - 1 if index > 0 else index + 1
             return self.load_data(index), index
 
+    def _device_aug_on(self):
+        """cfg.dataset.device_aug (set by the trainer's loader): workers draw the plan, the device executes it; only with
+        device_transform, i.e. for consumers that take uint8 batches"""
+        return bool(getattr(self, "device_aug", False)) and bool(getattr(self, "device_transform", False))
+
+    def _device_aug_item(self, img, lbl, path, seed, paste):
+        """the sample as plan + the bytes the plan reads (device_aug.pack_sample), or — a plan with a transform that has no
+        device form — as finished uint8 views from the host code, the draws spent once either way"""
+        import random
+        if seed is not None:
+            random.seed(seed)
+        state = random.getstate()
+        plan = device_aug.plan_sample(self.aug_fun, img.shape[:2])
+        cp_mask = None
+        if device_aug.needs_host(plan):
+            random.setstate(state)
+            if paste:
+                img, lbl, cp_mask = self.preprocessor.run(img, lbl)
+            img, lbl = augmentations.aug(self.aug_fun, img, lbl)
+            out = device_aug.pack_finished(*utils.transform(img, lbl, raw_u8=True))
+        else:
+            y1, y2, x1, x2 = device_aug.plan_window(plan)
+            src = None
+            if paste:
+                src, cp_mask = self.preprocessor.run_plan(img, lbl)
+                if src is not None:
+                    src = (src[0][y1:y2, x1:x2], src[1][y1:y2, x1:x2], src[2])
+            out = device_aug.pack_sample(plan, img[y1:y2, x1:x2], lbl[y1:y2, x1:x2], src)
+        out["image_paths"] = path
+        if cp_mask is not None:
+            out["copy_paste_mask"] = torch.from_numpy(cp_mask)
+        return out
+
     def original_get_item(self, index):
         (img, lbl, path), index = self._safe_load(index)
+        if self._device_aug_on():
+            return self._device_aug_item(img, lbl, path, index, False)
         img, lbl = augmentations.aug(self.aug_fun, img, lbl, index)
         img, lbl = utils.transform(img, lbl, raw_u8=getattr(self, "device_transform", False))
         return {"images": img, "labels": lbl, "image_paths": path}
 
     def get_item_with_copy_paste(self, index):
         (img, lbl, path), index = self._safe_load(index)
+        if self._device_aug_on():
+            return self._device_aug_item(img, lbl, path, None, True)
         img, lbl, cp_mask = self.preprocessor.run(img, lbl)
         img, lbl = augmentations.aug(self.aug_fun, img, lbl)
         img, lbl = utils.transform(img, lbl, raw_u8=getattr(self, "device_transform", False))

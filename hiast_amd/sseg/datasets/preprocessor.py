@@ -55,6 +55,27 @@ class CopyPaste:
             raise NotImplementedError("copy_paste.mode %r" % self.cfg.preprocessor.copy_paste.mode)
         return self.run_original(img, lbl)
 
+    def run_plan(self, img, lbl):
+        """the device_aug form of run(): the same np.random draws and the same source image, but nothing is composited —
+        -> ((source image, source label, uint8[256] table: 1 = hard class) or None, copy_paste_mask).  The device takes the
+        composite per pixel (table[lbl_src] ? source : own) on the crop window before it resamples; a per-pixel select
+        commutes with the crop, so the result is run_original()'s followed by the crop.  The mask stays host-computed at
+        native resolution."""
+        if self.cfg.preprocessor.copy_paste.mode != "original":
+            raise NotImplementedError("copy_paste.mode %r" % self.cfg.preprocessor.copy_paste.mode)
+        mask = np.full(lbl.shape, 255, dtype=np.uint8)
+        c = self.random_select(self.hard_classes)
+        if c is None:
+            return None, mask
+        name = np.random.choice(self.samples_with_class[c])
+        img_, lbl_, _ = self.dataset_copy_from.load_data(self.dataset_copy_from.get_file_to_idx(name))
+        if img.shape != img_.shape:
+            img_, lbl_ = self.resize(img_, lbl_, lbl.shape)
+        table = np.zeros(256, dtype=np.uint8)
+        table[np.asarray(self.hard_classes, dtype=np.int64)] = 1
+        np.copyto(mask, lbl_, where=table[lbl_] != 0)
+        return (img_, lbl_, table), mask
+
     def random_select(self, selected_classes):
         """rejection-sample a hard class (preprocessor.py:70-77).  Deviations: a class that no pseudo-labelled
         image contains is rejected too (the reference would raise in np.random.choice on its empty file list), and

@@ -70,6 +70,20 @@ def to_device_batch(images, labels, device):
     return imgs, lbls
 
 
+def assemble_device_batch(batch, device):
+    """a batch collated by a device_aug dataset (plans + raw bytes, device_aug.collate) -> what to_device_batch returns for
+    the same samples read without device_aug, bit for bit: the device executes the plans (hiast_aug_*_u8) and normalises"""
+    from hiast_amd.sseg.datasets import device_aug
+    return device_aug.assemble_device_batch(batch, device)
+
+
+def batch_to_device(batch, device):
+    """one DataLoader batch (dict) -> (images, labels) on the device, whichever way its dataset hands samples over"""
+    if "device_aug" in batch:
+        return assemble_device_batch(batch, device)
+    return to_device_batch(batch["images"], batch["labels"], device)
+
+
 def preprocess_label(lbl, id_map, ignored_index=255):
     assert lbl.ndim == 2, "Only label with shape of [H, W] is valid"
     out = np.full(lbl.shape, ignored_index, dtype=np.uint8)

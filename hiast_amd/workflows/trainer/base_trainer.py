@@ -167,6 +167,14 @@ class BaseTrainer:
         sampler = DistributedSampler(ds, num_replicas=self.world, rank=self.gpu_index, shuffle=shuffle)
         nw = self.cfg.dataset.num_workers
         kw = dict(num_workers=nw, pin_memory=True, persistent_workers=nw > 0, worker_init_fn=_worker_init if nw > 0 else None)
+        # cfg.dataset.device_aug / HIAST_DEVICE_AUG=1 (training loaders only; off by default): workers draw every random
+        # decision and hand over the crop window's bytes + the plan, the device resamples and recolours (device_aug.py)
+        ds.device_aug = (ds.device_transform and shuffle and drop_last
+                         and (bool(getattr(self.cfg.dataset, "device_aug", False))
+                              or os.environ.get("HIAST_DEVICE_AUG", "0") == "1"))
+        if ds.device_aug:
+            from hiast_amd.sseg.datasets import device_aug
+            kw["collate_fn"] = device_aug.collate
         if shuffle and drop_last and os.environ.get("HIAST_EPOCH_RESTART", "0") != "1":
             # training loaders: one endless iterator over the epochs (same batches, no restart at the boundaries)
             return sampler, DataLoader(ds, batch_sampler=_EpochChain(sampler, batch_size, drop_last), **kw)

@@ -180,6 +180,23 @@ class ConsistencySelfTrainingTrainer(BaseTrainer):
 
     def train(self):
         t = self.next_target_batch()
+        if "device_aug" in t:                   # cfg.dataset.device_aug: the device executes the workers' plans
+            img, plbl = du.assemble_device_batch(t, self.device)
+            if isinstance(img, (list, tuple)):
+                assert len(img) == 2 and plbl[0] is plbl[1]
+                weak, strong, plbl = img[0], img[1], plbl[0]
+            else:
+                weak = strong = img
+        else:
+            weak, strong, plbl = self._host_batch_to_device(t)
+        if self.graph_train_enabled():
+            # forward + backward from a captured HIP graph (GraphedTrainStep): update_model() finds the gradients in place
+            if getattr(self, "_graphed_step", None) is None:
+                self._graphed_step = GraphedTrainStep(self)
+            return self._graphed_step(weak, strong, plbl)      # (StepLosses: carries the "backward has run" marker)
+        return self.train_on(weak, strong, plbl)
+
+    def _host_batch_to_device(self, t):
         img, plbl = t["images"], t["labels"]
         if isinstance(img, (list, tuple)):
             assert len(img) == 2 and torch.equal(plbl[0], plbl[1])
@@ -191,12 +208,7 @@ class ConsistencySelfTrainingTrainer(BaseTrainer):
             strong = weak
         else:
             (weak, strong), plbl = du.to_device_batch([weak, strong], plbl, self.device)
-        if self.graph_train_enabled():
-            # forward + backward from a captured HIP graph (GraphedTrainStep): update_model() finds the gradients in place
-            if getattr(self, "_graphed_step", None) is None:
-                self._graphed_step = GraphedTrainStep(self)
-            return self._graphed_step(weak, strong, plbl)      # (StepLosses: carries the "backward has run" marker)
-        return self.train_on(weak, strong, plbl)
+        return weak, strong, plbl
 
     def graph_train_enabled(self):
         """on by default for 16-bit single-process training (HIAST_GRAPH_TRAIN=0, read once, keeps every iteration eager):

@@ -463,6 +463,36 @@ int hiast_maxpool3x3s2_nhwc_bwd(const void* dy, const uint8_t* idx, void* dx, in
 int hiast_normalize_u8(const uint8_t* img, float* out, int B, int64_t HW, const float* mean, const float* std,
                        hiast_stream_t stream);
 
+/* ---- K15: the per-sample data path on the device (cfg.dataset.device_aug) -----------------------------
+ * augmentations.py / preprocessor.py of the reference run in DataLoader workers; here a worker hands over bytes and a
+ * PLAN (every random decision, drawn on the host: hiast_amd/sseg/datasets/device_aug.py) and the device executes it,
+ * byte-identical to the host code.  A batch is ONE uint8 blob, ONE int32 table blob and one int64 record row per
+ * sample, all on the device; every offset counts elements of its blob:
+ *   recs [B][HIAST_AUG_REC_WORDS]: kind (0 plan | 1 finished views: copied), img, lbl, paste_img, paste_lbl, paste_table
+ *        (blob offsets; paste_* = -1 without CopyPaste), ch, cw (extent of the handed-over window), flip, then table
+ *        offsets hlo, hn, hk, h_taps, vlo, vn, vk, v_taps (first tap / tap count / [out][taps] 22-bit fixed-point
+ *        weights per output column / row: Pillow's 8-bit resample), nx, ny (nearest source index per output column / row)
+ *   ops  [B][HIAST_AUG_OPS_WORDS] of ONE view: kind, blob offset of the finished view (kind 1), n_ops, 0, then
+ *        (type, blob offset of a 256-entry table) x HIAST_AUG_MAX_OPS; at most one HIAST_AUG_OP_EQUALIZE per row.
+ * hiast_aug_geometry_u8: CopyPaste select on load (table[paste_lbl] ? paste : own), flipped read, horizontal pass into
+ *   tmp [B][max_ch][ow][3] (rounded to uint8), vertical pass -> img_out uint8 [B][oh][ow][3]; label gather through the
+ *   same select -> lbl_out uint8 [B][oh][ow].  Two launches.
+ * hiast_aug_hist_u8: per sample with an Equalize in its row, the per-channel histogram of `in` after the ops before it
+ *   (hist uint32 [B][3][256], zeroed here) and cv2.equalizeHist's tables from it (eq_lut uint8 [B][3][256]).
+ * hiast_aug_colour_u8: a view's op row on in uint8 [B][HW][3] -> out (a different buffer). */
+#define HIAST_AUG_REC_WORDS 20
+#define HIAST_AUG_MAX_OPS 8
+#define HIAST_AUG_OPS_WORDS (4 + 2 * HIAST_AUG_MAX_OPS)
+#define HIAST_AUG_OP_LUT 1
+#define HIAST_AUG_OP_GRAY 2
+#define HIAST_AUG_OP_EQUALIZE 3
+int hiast_aug_geometry_u8(const int64_t* recs, const uint8_t* blob, const int32_t* tabs, uint8_t* tmp,
+                          uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow, hiast_stream_t stream);
+int hiast_aug_hist_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* in, uint32_t* hist, uint8_t* eq_lut,
+                      int B, int64_t HW, hiast_stream_t stream);
+int hiast_aug_colour_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* eq_lut, const uint8_t* in,
+                        uint8_t* out, int B, int64_t HW, hiast_stream_t stream);
+
 /* K11b: copy n_tensors small tensors in one launch (the BatchNorm buffers update_ema_model copies from the student,
  * utils/utils.py:120-123).  table: device array of {dst, src, nbytes}; one block per tensor. */
 typedef struct { void* dst; const void* src; int64_t nbytes; } hiast_copy_rec;

@@ -3,7 +3,8 @@ on N synthetic Cityscapes-size (2048x1024) target images whose pseudo-labels wer
 (PNG decode + CopyPaste + flip / random-sized crop / resize to 1024x512 + two colour views in DataLoader worker
 processes -> H2D -> teacher forward, student forward/backward, Adam, EMA).  Prints images/s including the host data path
 next to the compute-only number bench.py reports.
-    python tools/run_trainer_synth.py [N=32] [batch=8] [workers=14] [iters=24] [native_h=1024] [native_w=2048]"""
+    python tools/run_trainer_synth.py [N=32] [batch=8] [workers=14] [iters=24] [native_h=1024] [native_w=2048] [device_aug=0]
+device_aug=1: cfg.dataset.device_aug — the workers plan, the device crops / resamples / recolours."""
 import os
 import shutil
 import sys
@@ -35,6 +36,7 @@ nw = int(sys.argv[3]) if len(sys.argv) > 3 else 14
 iters = int(sys.argv[4]) if len(sys.argv) > 4 else 24
 nh = int(sys.argv[5]) if len(sys.argv) > 5 else 1024
 nwid = int(sys.argv[6]) if len(sys.argv) > 6 else 2048
+dev_aug = bool(int(sys.argv[7])) if len(sys.argv) > 7 else False
 root = tempfile.mkdtemp(prefix="hiast_train_")
 try:
     t0 = time.time()
@@ -68,6 +70,8 @@ try:
     cfg.cst_training.is_enabled = True
     cfg.cst_training.cst_loss.weight = 0.5
     cfg.preprocessor.type = "CopyPaste"
+    cfg.dataset.device_aug = dev_aug
+    TO_DEVICE = "assemble_device_batch" if dev_aug else "to_device_batch"     # the call of du that a batch goes through
     cfg.work_dir = os.path.join(root, "work")
     def measure(tag, warm=6):
         tr = TRAINER[cfg.trainer](cfg, 0)
@@ -94,7 +98,7 @@ try:
                     parts[key] = parts.get(key, 0.0) + time.perf_counter() - t
                     return r
                 setattr(obj, name, g)
-            wrap(du_, "to_device_batch", "to_device_batch")
+            wrap(du_, TO_DEVICE, TO_DEVICE)
             wrap(tr, "train_on", "train_on (teacher + student forward, loss)")
             wrap(tr, "update_model", "update_model (backward, Adam)")
             wrap(tr, "after_update", "after_update (EMA)")
@@ -128,8 +132,8 @@ try:
         if parts:
             print("  breakdown (ms/iter): " + ", ".join("%s %.1f" % (k, v / iters * 1e3) for k, v in parts.items()), flush=True)
         del tr.next_target_batch                # (the instance attribute; the class method is back)
-        print("ConsistencySelfTrainingTrainer end to end, %s (DataLoader, %d workers, CopyPaste + MS + CCA, bs %d): "
-              "%.1f ms/iter = %.1f images/s" % (tag, nw, bs, dt * 1e3, bs / dt), flush=True)
+        print("ConsistencySelfTrainingTrainer end to end, %s (DataLoader, %d workers, CopyPaste + MS + CCA, bs %d, device_aug %s): "
+              "%.1f ms/iter = %.1f images/s" % (tag, nw, bs, "on" if dev_aug else "off", dt * 1e3, bs / dt), flush=True)
         # host data path alone: how fast can the workers deliver batches?
         t0 = time.time()
         for _ in range(iters):
@@ -144,15 +148,15 @@ try:
             time.sleep(3.0)                     # the workers fill their prefetch queues and go idle
             tr.next_target_batch = lambda: b
             for label, resident in (("host-resident", False), ("device-resident", True)):
-                orig = du_.to_device_batch
+                orig = getattr(du_, TO_DEVICE)
                 if resident:
                     cache = {}
 
-                    def cached(imgs, lbl, dev, _o=orig, _c=cache):
+                    def cached(*a, _o=orig, _c=cache):
                         if "v" not in _c:
-                            _c["v"] = _o(imgs, lbl, dev)
+                            _c["v"] = _o(*a)
                         return _c["v"]
-                    du_.to_device_batch = cached
+                    setattr(du_, TO_DEVICE, cached)
                 try:
                     for it in range(3):
                         tr.step(10 ** 5 + it)
@@ -164,7 +168,7 @@ try:
                     torch.cuda.synchronize()
                     dt = (time.time() - t0) / iters
                 finally:
-                    du_.to_device_batch = orig
+                    setattr(du_, TO_DEVICE, orig)
                 print("  one %s batch, workers idle: %.1f ms/iter (host loop %.1f)" % (label, dt * 1e3, th * 1e3), flush=True)
             del tr.next_target_batch
         tr.t_iter = tr.t_loader = None          # stop this trainer's worker processes before the next measurement
@@ -173,7 +177,8 @@ try:
         gc.collect()
         torch.cuda.empty_cache()
 
-    measure("PNG decode per sample (reference behaviour)")
+    if os.environ.get("HIAST_E2E_CACHE_ONLY", "0") != "1":      # (=1: only the decoded-cache measurement below)
+        measure("PNG decode per sample (reference behaviour)")
     # decoded-image cache (cfg.dataset.decoded_cache_dir): every image / pseudo-label is decoded once, then re-read as raw bytes
     dcache = tempfile.mkdtemp(prefix="hiast_dcache_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     cfg.dataset.decoded_cache_dir = dcache
