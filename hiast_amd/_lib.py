@@ -98,6 +98,9 @@ SIGNATURES = {
     "hiast_aug_geometry_u8": (c_int, [c_vp] * 6 + [c_int] * 4 + [c_vp]),
     "hiast_aug_hist_u8": (c_int, [c_vp] * 5 + [c_int, c_i64, c_vp]),
     "hiast_aug_colour_u8": (c_int, [c_vp] * 5 + [c_int, c_i64, c_vp]),
+    "hiast_aug2_table_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
+    "hiast_aug2_colour_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
+    "hiast_aug2_blur_u8": (c_int, [c_vp] * 5 + [c_int] * 3 + [c_vp]),
     "hiast_adam_prepare": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "hiast_adam_step": (c_int, [c_vp, c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, c_f32, c_f32, c_vp, c_vp]),
     "hiast_confusion_hist": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -629,6 +629,7 @@ def multi_copy(plan):
 # ------------------------------------------------------------------------------- K15 device-side sample path
 AUG_REC_WORDS, AUG_MAX_OPS = 20, 8
 AUG_OPS_WORDS = 4 + 2 * AUG_MAX_OPS
+AUG_MAX_KSIZE = 41
 
 
 def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
@@ -683,11 +684,26 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
             if o[0] != 0 or not 0 <= o[2] <= AUG_MAX_OPS:
                 raise ValueError("device_aug: sample %d view %d: kind %d with %d ops" % (b, k, o[0], o[2]))
             types = [o[4 + 2 * i] for i in range(o[2])]
-            if any(t not in (1, 2, 3) for t in types) or types.count(3) > 1:
+            if any(t not in (1, 2, 3, 4, 5, 6, 7) for t in types) or (max(types, default=0) <= 3 and types.count(3) > 1):
                 raise ValueError("device_aug: sample %d view %d: op types %s" % (b, k, types))
             for i, t in enumerate(types):
+                par = o[5 + 2 * i]
                 if t == 1:
-                    inside(o[5 + 2 * i], 256, blob_n, "view %d LUT %d" % (k, i), b)
+                    inside(par, 256, blob_n, "view %d LUT %d" % (k, i), b)
+                elif t in (4, 5):          # contrast / saturation: the bits of a float64 factor
+                    if not np.isfinite(np.array([par], np.int64).view(np.float64)[0]):
+                        raise ValueError("device_aug: sample %d view %d: op %d has a non-finite factor" % (b, k, i))
+                elif t == 6:
+                    if not 0 <= par <= 255:
+                        raise ValueError("device_aug: sample %d view %d: hue shift %d" % (b, k, par))
+                elif t == 7:               # blur: weights offset | ksize << 32
+                    ksize, off = par >> 32, par & 0xFFFFFFFF
+                    if not (3 <= ksize <= AUG_MAX_KSIZE and ksize % 2 == 1 and ksize // 2 < min(oh, ow)):
+                        raise ValueError("device_aug: sample %d view %d: blur of %d taps on %dx%d" % (b, k, ksize, oh, ow))
+                    inside(off, ksize, tabs.size, "view %d blur weights" % k, b)
+                    w = tabs[off:off + ksize].view(np.float32)
+                    if not (np.isfinite(w).all() and np.array_equal(w, w[::-1])):
+                        raise ValueError("device_aug: sample %d view %d: blur weights not finite and symmetric" % (b, k))
 
 
 def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch):
@@ -727,6 +743,64 @@ def aug_colour_u8(img_u8, ops, blob, equalize=True):
     return out
 
 
+def _aug_segments(ops_view):
+    """one view's op rows (numpy int64 [B, 20]) -> int32 [R, B, 4] = (from, to, stat, blur) per launch round and sample
+    (include/hiast_hip.h, K15b): a segment ends before a second table op (Equalize 3 / contrast 4) and after a blur (7)"""
+    B = ops_view.shape[0]
+    rounds = []
+    pos = [0] * B
+    n = [int(r[2]) if int(r[0]) == 0 else 0 for r in ops_view]
+    while True:
+        seg = np.full((B, 4), -1, np.int32)
+        for b in range(B):
+            i, stat = pos[b], -1
+            while i < n[b]:
+                t = int(ops_view[b, 4 + 2 * i])
+                if t == 7 or (t in (3, 4) and stat >= 0):
+                    break
+                if t in (3, 4):
+                    stat = i
+                i += 1
+            blur = i if i < n[b] and int(ops_view[b, 4 + 2 * i]) == 7 else -1
+            seg[b] = (pos[b], i, stat, blur)
+            pos[b] = i + (blur >= 0)
+        rounds.append(seg)
+        if all(p >= m for p, m in zip(pos, n)):
+            return np.stack(rounds)
+
+
+def aug2_view_u8(img_u8, ops, ops_h, blob, tabs):
+    """one view's op rows with level-2 ops (ops int64 [B, 20] on the device, ops_h the same rows on the host, bounds-checked
+    by the caller) on uint8 [B, H, W, 3] -> a new tensor: the first segment out of place, the others in place"""
+    _req(img_u8, torch.uint8, 4, "img_u8")
+    _req(ops, torch.int64, 2, "ops")
+    _req(blob, torch.uint8, 1, "blob")
+    _req(tabs, torch.int32, 1, "tabs")
+    B, H, W, three = img_u8.shape
+    assert three == 3 and tuple(ops.shape) == tuple(ops_h.shape) == (B, AUG_OPS_WORDS)
+    lib, dev = _lib.load(), img_u8.device
+    segs_h = _aug_segments(ops_h)
+    segs = torch.from_numpy(segs_h).pin_memory().to(dev, non_blocking=True)
+    table = torch.empty((B, 3, 256), dtype=torch.uint8, device=dev)
+    hist = torch.empty((B, 3, 256), dtype=torch.int32, device=dev)
+    out = torch.empty_like(img_u8)
+    tmp = None
+    for r in range(segs_h.shape[0]):
+        sg, src = segs[r], (img_u8 if r == 0 else out)
+        if (segs_h[r, :, 2] >= 0).any():
+            check(lib.hiast_aug2_table_u8(_ptr(ops), _ptr(sg), _ptr(blob), _ptr(src), _ptr(hist), _ptr(table), B, H * W,
+                                          _stream()), "hiast_aug2_table_u8")
+        if r == 0 or (segs_h[r, :, 1] > segs_h[r, :, 0]).any():
+            check(lib.hiast_aug2_colour_u8(_ptr(ops), _ptr(sg), _ptr(blob), _ptr(table), _ptr(src), _ptr(out), B, H * W,
+                                           _stream()), "hiast_aug2_colour_u8")
+        if (segs_h[r, :, 3] >= 0).any():
+            if tmp is None:
+                tmp = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+            check(lib.hiast_aug2_blur_u8(_ptr(ops), _ptr(sg), _ptr(tabs), _ptr(out), _ptr(tmp), B, H, W, _stream()),
+                  "hiast_aug2_blur_u8")
+    return out
+
+
 def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
     """HOST tensors of a collated device_aug batch (device_aug.build_batch_tables) -> ([uint8 [B, oh, ow, 3] per view],
     uint8 label [B, oh, ow]) on `device`: four uploads, then geometry + one colour pass per view"""
@@ -747,8 +821,12 @@ def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
         has_ops = bool((ops_h[k, planned, 2] > 0).any())
         if has_ops or (k > 0 and not planned.all()):       # (finished samples: view k is copied in from the blob)
             n = ops_h[k, :, 2]
-            eq = bool(((ops_h[k][:, 4::2] == 3) & (np.arange(AUG_MAX_OPS)[None, :] < n[:, None]) & planned[:, None]).any())
-            cur = aug_colour_u8(cur, ops_d[k], blob_d, equalize=eq)
+            live = (np.arange(AUG_MAX_OPS)[None, :] < n[:, None]) & planned[:, None]
+            if bool(((ops_h[k][:, 4::2] > 3) & live).any()):      # level 2: ColorJitter / GaussianBlur ops, in segments
+                cur = aug2_view_u8(cur, ops_d[k], ops_h[k], blob_d, tabs_d)
+            else:
+                eq = bool(((ops_h[k][:, 4::2] == 3) & live).any())
+                cur = aug_colour_u8(cur, ops_d[k], blob_d, equalize=eq)
         views.append(cur)
     return views, lbl
 

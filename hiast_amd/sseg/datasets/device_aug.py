@@ -30,6 +30,8 @@ MAX_OPS = 8                  # colour ops per view the device record holds (afte
 HOST_ONLY = (A.ColorJitter, A.GaussianBlur, A.FDA)
 
 OP_LUT, OP_GRAY, OP_EQUALIZE = 1, 2, 3
+OP_CONTRAST, OP_SAT, OP_HUE, OP_BLUR = 4, 5, 6, 7        # level 2 (plan_sample(level=2)): ColorJitter's steps, GaussianBlur
+MAX_KSIZE = 41
 
 
 # ------------------------------------------------------------------------------------------------- tables
@@ -179,7 +181,8 @@ def _lut_of(t, params):
 class _Walker:
     """one chain of views: the walk of augmentations.aug() with its draws, recording instead of touching pixels"""
 
-    def __init__(self, in_shape):
+    def __init__(self, in_shape, level=1):
+        self.level = level
         self.geom = _GeomState(in_shape)
         self.geom_open = True                    # no pixel op recorded yet: geometry may still be folded into view 0's op
         self.ops = []
@@ -246,6 +249,18 @@ class _Walker:
             if t.h > H or t.w > W:
                 raise ValueError("RandomCrop: crop %dx%d is larger than the image %dx%d" % (t.h, t.w, H, W))
             self._geom_op(self.geom_open and g.do_crop(*A._crop_coords(H, W, t.h, t.w, params["h_start"], params["w_start"])))
+        elif self.level >= 2 and isinstance(t, A.ColorJitter):
+            for i in params["order"]:
+                op = _jitter_op(i, params["factors"][i])
+                if op is not None:
+                    self._pixel_op(op)
+        elif self.level >= 2 and isinstance(t, A.GaussianBlur):
+            if params["ksize"] > 1:
+                k = params["ksize"]
+                if k % 2 != 1 or k > MAX_KSIZE or k // 2 >= min(g.shape()):     # (the device reflects a border once)
+                    self._pixel_op(("host", "GaussianBlur"))
+                else:
+                    self._pixel_op(("blur", blur_weights(k, params["sigma"])))
         elif isinstance(t, HOST_ONLY):
             self._pixel_op(("host", type(t).__name__))
         elif isinstance(t, (A.RandomContrast, A.RandomBrightness, A.Posterize, A.Solarize)):
@@ -260,13 +275,34 @@ class _Walker:
             self._pixel_op(("host", type(t).__name__))
 
 
-def plan_sample(aug_fun, in_shape, index=None):
+def _jitter_op(i, f):
+    """step i (0 brightness, 1 contrast, 2 saturation, 3 hue) of A.ColorJitter.apply with its drawn factor as a plan op;
+    None = the bytes unchanged (a hue factor of exactly 0)"""
+    if i == 0:
+        return ("lut", np.clip(np.arange(256, dtype=np.float32) * f, 0, 255).astype(np.uint8))
+    if i == 1:
+        return ("contrast", float(f))
+    if i == 2:
+        return ("sat", float(f))
+    if f == 0:
+        return None
+    return ("hue", int(round(256 * f)) % 256)         # also 0: the HSV round trip is not the identity
+
+
+def blur_weights(ksize, sigma):
+    w = A._gaussian_kernel_cv(ksize, sigma)
+    assert w.dtype == np.float32 and np.array_equal(w, w[::-1])      # scipy's symmetric-filter loop is the definition
+    return w
+
+
+def plan_sample(aug_fun, in_shape, index=None, level=1):
     """-> list of view plans (one per view; a single aug gives a list of one).  Consumes exactly the draws
     augmentations.aug(aug_fun, img, lbl, index) consumes unless the plan `needs_host` through an FDA, whose parameters read
-    the image: the caller restores the state it saved and runs aug() (see BaseDataset)."""
+    the image: the caller restores the state it saved and runs aug() (see BaseDataset).  level 2: ColorJitter and
+    GaussianBlur are plan ops too (("contrast", f), ("sat", f), ("hue", shift), ("blur", weights))."""
     if index is not None:
         random.seed(index)
-    w = _Walker(in_shape)
+    w = _Walker(in_shape, level)
     views = []
     for f in (aug_fun if isinstance(aug_fun, (list, tuple)) else [aug_fun]):
         w.begin_view()
@@ -335,9 +371,108 @@ def execute_geometry_host(g, raw_img, raw_lbl, paste=None):
     return np.ascontiguousarray(out), np.ascontiguousarray(raw_lbl[g.ny][:, g.nx])
 
 
+def _f32div(a, b):
+    return (a.astype(np.float32) / b.astype(np.float32)).astype(np.float32)
+
+
+def rgb_to_hsv_u8(img):
+    """Pillow's convert("HSV") (rgb2hsv_row) on uint8 [..., 3], byte for byte: float32 quotients, the hue wrapped in
+    float64, H and S truncated"""
+    f32, f64 = np.float32, np.float64
+    r, g, b = img[..., 0], img[..., 1], img[..., 2]
+    maxc, minc = img.max(-1), img.min(-1)
+    flat = maxc == minc
+    cr = np.where(flat, 1, maxc - minc).astype(f32)
+    s = _f32div(cr, np.maximum(maxc, 1))
+    rc, gc, bc = _f32div(maxc - r, cr), _f32div(maxc - g, cr), _f32div(maxc - b, cr)
+    h = np.where(r == maxc, bc - gc,
+                 np.where(g == maxc, (2.0 + rc.astype(f64) - bc.astype(f64)).astype(f32),
+                          (4.0 + gc.astype(f64) - rc.astype(f64)).astype(f32)))
+    hd = h.astype(f64) / 6.0 + 1.0
+    h = (hd - np.floor(hd)).astype(f32)                               # fmod(x, 1.0) of a positive x
+    H = np.clip((h.astype(f64) * 255.0).astype(np.int32), 0, 255)
+    S = np.clip((s.astype(f64) * 255.0).astype(np.int32), 0, 255)
+    return np.stack([np.where(flat, 0, H), np.where(flat, 0, S), maxc], -1).astype(np.uint8)
+
+
+def hsv_to_rgb_u8(hsv):
+    """Pillow's HSV -> RGB (hsv2rgb_row) on uint8 [..., 3], byte for byte: p, q, t in float64 from the float32 fraction and
+    saturation, C round() (half away from zero)"""
+    f32, f64 = np.float32, np.float64
+    h, s, v = hsv[..., 0], hsv[..., 1], hsv[..., 2]
+    h6 = h.astype(f64) * 6.0 / 255.0
+    fl = np.floor(h6)
+    f = (h6 - fl).astype(f32)
+    fs = (s.astype(f64) / 255.0).astype(f32)
+    vd = v.astype(f64)
+    rnd = lambda x: np.clip(np.floor(x + 0.5), 0, 255).astype(np.uint8)       # noqa: E731  (x >= 0 here)
+    p = rnd(vd * (1.0 - fs.astype(f64)))
+    q = rnd(vd * (1.0 - fs.astype(f64) * f.astype(f64)))
+    t = rnd(vd * (1.0 - fs.astype(f64) * (1.0 - f.astype(f64))))
+    i = fl.astype(np.int32) % 6
+    out = np.stack([np.choose(i, [v, q, p, p, t, v]), np.choose(i, [t, v, v, q, p, p]), np.choose(i, [p, p, t, v, v, q])], -1)
+    return np.where((s == 0)[..., None], v[..., None], out).astype(np.uint8)
+
+
+def hue_u8(img, shift):
+    """A.ColorJitter._hue for a non-zero factor: shift = int(round(256 * f)) mod 256"""
+    out = np.empty_like(img)
+    flat_i, flat_o = img.reshape(-1, 3), out.reshape(-1, 3)
+    for a in range(0, flat_i.shape[0], 1 << 20):                      # (bounded float64 temporaries)
+        hsv = rgb_to_hsv_u8(flat_i[a:a + (1 << 20)])
+        hsv[..., 0] = (hsv[..., 0].astype(np.int32) + int(shift)) % 256
+        flat_o[a:a + (1 << 20)] = hsv_to_rgb_u8(hsv)
+    return out
+
+
+def contrast_lut(img, f):
+    """the table A.ColorJitter._contrast applies to `img`: the gray mean as an exact integer sum / count in float64"""
+    mean = np.float64(int(A._gray_cv(img).sum(dtype=np.int64))) / np.float64(img.shape[0] * img.shape[1])
+    v = np.arange(256, dtype=np.float32) * np.float32(f) + np.float32(mean * (1.0 - f))
+    return np.clip(v, 0, 255).astype(np.uint8)
+
+
+def saturation_u8(img, f):
+    """A.ColorJitter._saturation: c * f32(f) + gray * f32(1 - f), every operation rounded to float32, truncated"""
+    g = A._gray_cv(img).astype(np.float32) * np.float32(1 - f)
+    out = img.astype(np.float32) * np.float32(f) + g[..., None]
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def blur_pass(x, w, axis):
+    """one pass of scipy.ndimage.correlate1d(x float32, w float32 symmetric, mode="mirror") restated: float64,
+    o = x[c] * w[s]; o += (x[c - j] + x[c + j]) * w[s - j] for j = s .. 1, rounded to float32 once"""
+    x = np.moveaxis(np.asarray(x, np.float32), axis, 0).astype(np.float64)
+    w = np.asarray(w, np.float32).astype(np.float64)
+    n, s = x.shape[0], len(w) // 2
+    if s >= n:
+        raise ValueError("blur: half width %d reaches across the axis of %d" % (s, n))
+    idx = np.abs(np.arange(-s, n + s))
+    idx = np.where(idx >= n, 2 * (n - 1) - idx, idx)
+    xp = x[idx]
+    o = xp[s:s + n] * w[s]
+    for j in range(s, 0, -1):
+        o = o + (xp[s - j:s - j + n] + xp[s + j:s + j + n]) * w[s - j]
+    return np.ascontiguousarray(np.moveaxis(o.astype(np.float32), 0, axis))
+
+
+def blur_u8(img, w):
+    """A._blur_separable: axis 0, then axis 1, rint (half to even), clip"""
+    x = blur_pass(blur_pass(img.astype(np.float32), w, 0), w, 1)
+    return np.clip(np.rint(x), 0, 255).astype(np.uint8)
+
+
 def execute_colour_host(ops, img):
     for op in ops:
-        if op[0] == "lut":
+        if op[0] == "contrast":
+            img = contrast_lut(img, op[1])[img]
+        elif op[0] == "sat":
+            img = saturation_u8(img, op[1])
+        elif op[0] == "hue":
+            img = hue_u8(img, op[1])
+        elif op[0] == "blur":
+            img = blur_u8(img, op[1])
+        elif op[0] == "lut":
             img = op[1][img]
         elif op[0] == "gray":
             img = np.repeat(A._gray_cv(img)[..., None], 3, axis=2)
@@ -469,6 +604,14 @@ def build_batch_tables(samples):
                     row[4 + 2 * i] = OP_GRAY
                 elif op[0] == "equalize":
                     row[4 + 2 * i] = OP_EQUALIZE
+                elif op[0] in ("contrast", "sat"):           # the full float64 draw, as its bits
+                    row[4 + 2 * i] = OP_CONTRAST if op[0] == "contrast" else OP_SAT
+                    row[5 + 2 * i] = np.array([op[1]], np.float64).view(np.int64)[0]
+                elif op[0] == "hue":
+                    row[4 + 2 * i], row[5 + 2 * i] = OP_HUE, int(op[1])
+                elif op[0] == "blur":                        # float32 weights (as bits) in the int32 table blob
+                    w = np.ascontiguousarray(op[1], np.float32)
+                    row[4 + 2 * i], row[5 + 2 * i] = OP_BLUR, tabs.add(w.view(np.int32)) | (len(w) << 32)
                 else:
                     raise ValueError("op %r has no device form" % (op[0],))
                 row[2] = i + 1

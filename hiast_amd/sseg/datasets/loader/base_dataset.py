@@ -78,7 +78,7 @@ class BaseDataset(Dataset):
         if seed is not None:
             random.seed(seed)
         state = random.getstate()
-        plan = device_aug.plan_sample(self.aug_fun, img.shape[:2])
+        plan = device_aug.plan_sample(self.aug_fun, img.shape[:2], level=int(getattr(self, "device_aug_level", 1)))
         cp_mask = None
         if device_aug.needs_host(plan):
             random.setstate(state)

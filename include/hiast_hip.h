@@ -493,6 +493,36 @@ int hiast_aug_hist_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* in
 int hiast_aug_colour_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* eq_lut, const uint8_t* in,
                         uint8_t* out, int B, int64_t HW, hiast_stream_t stream);
 
+/* ---- K15b: level 2 of the device-side sample path (cfg.dataset.device_aug_level: 2) ------------------------------
+ * ColorJitter and GaussianBlur as plan ops, byte-identical to hiast_amd/sseg/datasets/augmentations.py.  Further op
+ * types of an ops row; the second word of the pair is
+ *   HIAST_AUG_OP_CONTRAST  the bits of the float64 factor (the table is built on the device from the gray mean of the
+ *                          image at that point of the chain)
+ *   HIAST_AUG_OP_SAT       the bits of the float64 factor
+ *   HIAST_AUG_OP_HUE       the hue shift, 0..255 (Pillow's 8-bit HSV round trip; 0 is NOT the identity)
+ *   HIAST_AUG_OP_BLUR      tabs offset of the ksize float32 weights (as bits; symmetric) | ksize << 32, ksize odd in
+ *                          3..HIAST_AUG_MAX_KSIZE, ksize / 2 < min(H, W)
+ * The host cuts a row into segments, one launch round each: seg int32 [B][4] = (from, to, stat, blur): ops [from, to)
+ * are pointwise except for at most one table op (Equalize / contrast) at index stat (-1: none); a blur at index
+ * blur (-1: none) follows them.  A sample whose segment is empty is skipped.  Any number of table ops per row.
+ * hiast_aug2_table_u8: per sample with a table op, the histogram of `in` after ops [from, stat) (hist uint32
+ *   [B][3][256], zeroed here; contrast: the gray histogram in bins 0..255) and the op's table (uint8 [B][3][256]).
+ * hiast_aug2_colour_u8: ops [from, to) on in uint8 [B][HW][3] -> out.  in != out: every sample is written (finished
+ *   views are copied from the blob); in == out: samples with an empty segment are not touched.
+ * hiast_aug2_blur_u8: the segment's blur, in place on img uint8 [B][H][W][3] through tmp float32 [B][H][W][3]: scipy's
+ *   symmetric correlate1d in float64 down the rows, then along them, reflect-101, rint.  Two launches. */
+#define HIAST_AUG_OP_CONTRAST 4
+#define HIAST_AUG_OP_SAT 5
+#define HIAST_AUG_OP_HUE 6
+#define HIAST_AUG_OP_BLUR 7
+#define HIAST_AUG_MAX_KSIZE 41
+int hiast_aug2_table_u8(const int64_t* ops, const int32_t* seg, const uint8_t* blob, const uint8_t* in, uint32_t* hist,
+                        uint8_t* table, int B, int64_t HW, hiast_stream_t stream);
+int hiast_aug2_colour_u8(const int64_t* ops, const int32_t* seg, const uint8_t* blob, const uint8_t* table,
+                         const uint8_t* in, uint8_t* out, int B, int64_t HW, hiast_stream_t stream);
+int hiast_aug2_blur_u8(const int64_t* ops, const int32_t* seg, const int32_t* tabs, uint8_t* img, float* tmp, int B,
+                       int H, int W, hiast_stream_t stream);
+
 /* K11b: copy n_tensors small tensors in one launch (the BatchNorm buffers update_ema_model copies from the student,
  * utils/utils.py:120-123).  table: device array of {dst, src, nbytes}; one block per tensor. */
 typedef struct { void* dst; const void* src; int64_t nbytes; } hiast_copy_rec;

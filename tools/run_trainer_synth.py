@@ -4,7 +4,8 @@ on N synthetic Cityscapes-size (2048x1024) target images whose pseudo-labels wer
 processes -> H2D -> teacher forward, student forward/backward, Adam, EMA).  Prints images/s including the host data path
 next to the compute-only number bench.py reports.
     python tools/run_trainer_synth.py [N=32] [batch=8] [workers=14] [iters=24] [native_h=1024] [native_w=2048] [device_aug=0]
-device_aug=1: cfg.dataset.device_aug — the workers plan, the device crops / resamples / recolours."""
+device_aug=1: cfg.dataset.device_aug — the workers plan, the device crops / resamples / recolours (DESIGN §5);
+device_aug=2: the same at cfg.dataset.device_aug_level 2 (ColorJitter and GaussianBlur on the device too)."""
 import os
 import shutil
 import sys
@@ -36,7 +37,9 @@ nw = int(sys.argv[3]) if len(sys.argv) > 3 else 14
 iters = int(sys.argv[4]) if len(sys.argv) > 4 else 24
 nh = int(sys.argv[5]) if len(sys.argv) > 5 else 1024
 nwid = int(sys.argv[6]) if len(sys.argv) > 6 else 2048
-dev_aug = bool(int(sys.argv[7])) if len(sys.argv) > 7 else False
+aug_level = int(sys.argv[7]) if len(sys.argv) > 7 else 0
+assert aug_level in (0, 1, 2), "device_aug is 0, 1 or 2"
+dev_aug = aug_level > 0
 root = tempfile.mkdtemp(prefix="hiast_train_")
 try:
     t0 = time.time()
@@ -71,6 +74,7 @@ try:
     cfg.cst_training.cst_loss.weight = 0.5
     cfg.preprocessor.type = "CopyPaste"
     cfg.dataset.device_aug = dev_aug
+    cfg.dataset.device_aug_level = max(aug_level, 1)
     TO_DEVICE = "assemble_device_batch" if dev_aug else "to_device_batch"     # the call of du that a batch goes through
     cfg.work_dir = os.path.join(root, "work")
     def measure(tag, warm=6):
@@ -133,7 +137,7 @@ try:
             print("  breakdown (ms/iter): " + ", ".join("%s %.1f" % (k, v / iters * 1e3) for k, v in parts.items()), flush=True)
         del tr.next_target_batch                # (the instance attribute; the class method is back)
         print("ConsistencySelfTrainingTrainer end to end, %s (DataLoader, %d workers, CopyPaste + MS + CCA, bs %d, device_aug %s): "
-              "%.1f ms/iter = %.1f images/s" % (tag, nw, bs, "on" if dev_aug else "off", dt * 1e3, bs / dt), flush=True)
+              "%.1f ms/iter = %.1f images/s" % (tag, nw, bs, "level %d" % aug_level if dev_aug else "off", dt * 1e3, bs / dt), flush=True)
         # host data path alone: how fast can the workers deliver batches?
         t0 = time.time()
         for _ in range(iters):
