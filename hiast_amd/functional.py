@@ -174,6 +174,60 @@ def discriminator_input(logits_lr, size, entropy=False):
     return _DInputFn.apply(logits_lr, int(size[0]), int(size[1]), bool(entropy))
 
 
+class _DiscConvFn(torch.autograd.Function):
+    """one layer of the warm-up discriminator on the library's own kernels (K19): 4x4 / stride 2 / padding 1 convolution +
+    bias (+ LeakyReLU 0.2) in one launch; the backward takes the activation's gate from the saved output inside the
+    input- and weight-gradient kernels.  The weight-gradient launch is skipped when neither weight nor bias wants a gradient
+    (the `params=` path of FCDiscriminator with detached weights)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, weight, bias, leaky):
+        x, weight = x.contiguous(), weight.contiguous()
+        bias = bias.contiguous() if bias is not None else None
+        y = K.disc_conv_fwd(x, weight, bias, leaky)
+        ctx.save_for_backward(x, weight, y)
+        ctx.leaky, ctx.has_bias = leaky, bias is not None
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        dy = dy.float().contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        dx = K.disc_conv_dgrad(dy, y, weight, x.shape, ctx.leaky) if need_x else None
+        dw = db = None
+        if need_w or (need_b and ctx.has_bias):
+            dw, db = K.disc_conv_wgrad(x, dy, y, ctx.leaky, want_bias=need_b and ctx.has_bias)
+        return dx, (dw if need_w else None), (db if need_b else None), None
+
+
+def disc_conv_shapes_ok(x_shape, w_shape):
+    """shapes the discriminator-convolution kernels take: x [B,Cin,H,W] with H, W >= 2, weight [Cout,Cin,4,4], 1..4096
+    channels on either side, every tensor below 2^31 elements (host only: asks the library's size function)"""
+    x_shape, w_shape = tuple(x_shape), tuple(w_shape)
+    if len(x_shape) != 4 or len(w_shape) != 4 or w_shape[2:] != (4, 4) or w_shape[1] != x_shape[1]:
+        return False
+    B, Cin, H, W = x_shape
+    Cout = w_shape[0]
+    if B < 1 or not 1 <= Cin <= 4096 or not 1 <= Cout <= 4096 or H < 2 or W < 2 or max(B, H, W) >= 2 ** 31:
+        return False
+    return K.disc_conv_workspace_bytes(B, Cin, Cout, H, W) > 0
+
+
+def disc_conv_ok(x, weight):
+    """HF.disc_conv4x4s2 takes this (input, weight) pair: device tensors, both float32, shapes as disc_conv_shapes_ok"""
+    return (isinstance(x, torch.Tensor) and isinstance(weight, torch.Tensor) and x.is_cuda and weight.is_cuda
+            and x.dtype == torch.float32 and weight.dtype == torch.float32
+            and disc_conv_shapes_ok(x.shape, weight.shape))
+
+
+def disc_conv4x4s2(x, weight, bias, leaky):
+    """leaky_relu?(F.conv2d(x, weight, bias, stride=2, padding=1), 0.2) for a 4x4 weight (FCDiscriminator's layers)"""
+    return _DiscConvFn.apply(x, weight, bias, bool(leaky))
+
+
 def _sync_world(bn):
     """number of ranks a BatchNorm layer's statistics are summed over: 1 = no exchange (plain BN, or no process group);
     N > 1 = SyncBN over N ranks; 0 = SyncBN in the one-rank rehearsal (utils/comm.py: the exchange is issued, the count is

@@ -1594,3 +1594,81 @@ def conv_wgrad_group(jobs):
     check(lib.hiast_conv_wgrad_group_nhwc(ctypes.addressof(arr), n, fmt, _ptr(ws), ws.numel() * 4, _stream()),
           "hiast_conv_wgrad_group_nhwc")
     return outs
+
+
+# ------------------------------------------------------------------------------- K19 discriminator 4x4 / stride-2 convolutions
+def disc_conv_workspace_bytes(B, Cin, Cout, H, W):
+    """bytes of workspace the input- and weight-gradient launches of one layer need; 0 = a shape the kernels refuse (host only)"""
+    return int(_lib.load().hiast_disc_conv_workspace_bytes(int(B), int(Cin), int(Cout), int(H), int(W)))
+
+
+def _disc_conv_ws(x_shape, Cout, device):
+    B, Cin, H, W = x_shape
+    n = disc_conv_workspace_bytes(B, Cin, Cout, H, W)
+    if n == 0:
+        raise _lib.HiastLibraryError("hiast_disc_conv: unsupported shape x=%s Cout=%d" % (tuple(x_shape), Cout))
+    key = ("disc", device, torch.cuda.current_stream(device).cuda_stream)      # per stream: see conv_wgrad_small_nhwc
+    ws = _wgrad_ws.get(key)
+    if ws is None or ws.numel() * 4 < n:
+        ws = torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+        _wgrad_ws[key] = ws
+    return ws
+
+
+def _disc_conv_shapes(x, weight):
+    B, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, Cin, 4, 4):
+        raise ValueError("weight must be [Cout, %d, 4, 4], got %s" % (Cin, tuple(weight.shape)))
+    if H < 2 or W < 2:
+        raise ValueError("a 4x4 stride-2 padding-1 convolution needs H, W >= 2, got %s" % (tuple(x.shape),))
+    return B, Cin, Cout, H, W, (H - 2) // 2 + 1, (W - 2) // 2 + 1
+
+
+def disc_conv_fwd(x, weight, bias, leaky):
+    """x [B,Cin,H,W], weight [Cout,Cin,4,4], bias [Cout] or None, fp32 NCHW -> leaky_relu?(conv2d(x, w, b, stride 2, padding 1))"""
+    _req(x, torch.float32, 4, "x")
+    _req(weight, torch.float32, 4, "weight")
+    B, Cin, Cout, H, W, Ho, Wo = _disc_conv_shapes(x, weight)
+    if bias is not None:
+        _req(bias, torch.float32, 1, "bias")
+        assert bias.numel() == Cout
+    y = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    check(_lib.load().hiast_disc_conv_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), B, Cin, Cout, H, W, int(bool(leaky)),
+                                          _stream()), "hiast_disc_conv_fwd")
+    return y
+
+
+def disc_conv_dgrad(dy, y, weight, x_shape, leaky):
+    """dy, y [B,Cout,Ho,Wo] (y = the layer's saved output: the LeakyReLU gate), weight [Cout,Cin,4,4] -> dx [B,Cin,H,W]"""
+    _req(dy, torch.float32, 4, "dy")
+    _req(weight, torch.float32, 4, "weight")
+    x_shape = tuple(int(s) for s in x_shape)
+    B, Cin, Cout, H, W, Ho, Wo = _disc_conv_shapes(torch.empty(x_shape, device="meta"), weight)
+    assert tuple(dy.shape) == (B, Cout, Ho, Wo), (tuple(dy.shape), (B, Cout, Ho, Wo))
+    if leaky:
+        _req(y, torch.float32, 4, "y")
+        assert y.shape == dy.shape
+    ws = _disc_conv_ws(x_shape, Cout, dy.device)
+    dx = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
+    check(_lib.load().hiast_disc_conv_dgrad(_ptr(dy), _ptr(y if leaky else None), _ptr(weight), _ptr(dx), B, Cin, Cout, H, W,
+                                            int(bool(leaky)), _ptr(ws), ws.numel() * 4, _stream()), "hiast_disc_conv_dgrad")
+    return dx
+
+
+def disc_conv_wgrad(x, dy, y, leaky, want_bias=True):
+    """x [B,Cin,H,W], dy, y [B,Cout,Ho,Wo] -> (dW [Cout,Cin,4,4], db [Cout] or None); bit-reproducible (fixed-order second stage)"""
+    _req(x, torch.float32, 4, "x")
+    _req(dy, torch.float32, 4, "dy")
+    B, Cin, H, W = x.shape
+    Cout = dy.shape[1]
+    assert H >= 2 and W >= 2 and tuple(dy.shape) == (B, Cout, (H - 2) // 2 + 1, (W - 2) // 2 + 1), (tuple(x.shape), tuple(dy.shape))
+    if leaky:
+        _req(y, torch.float32, 4, "y")
+        assert y.shape == dy.shape
+    ws = _disc_conv_ws(tuple(x.shape), Cout, x.device)
+    dw = torch.empty((Cout, Cin, 4, 4), dtype=torch.float32, device=x.device)
+    db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    check(_lib.load().hiast_disc_conv_wgrad(_ptr(x), _ptr(dy), _ptr(y if leaky else None), _ptr(dw), _ptr(db), B, Cin, Cout, H, W,
+                                            int(bool(leaky)), _ptr(ws), ws.numel() * 4, _stream()), "hiast_disc_conv_wgrad")
+    return dw, db

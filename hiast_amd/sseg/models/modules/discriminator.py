@@ -1,8 +1,16 @@
 """FCDiscriminator (reference: sseg/models/modules/discriminator.py:7-33): five 4x4 stride-2 convolutions,
 C -> 64 -> 128 -> 256 -> 512 -> 1, LeakyReLU(0.2) between them; state-dict names conv1..conv4, classifier.
-31 GFLOP per 512x1024 image (4 % of one trunk forward): the convolutions go through MIOpen via PyTorch-ROCm."""
+31 GFLOP per 512x1024 image (4 % of one trunk forward).
+
+Default: the convolutions go through MIOpen via PyTorch-ROCm (F.conv2d, in the autocast type).  HIAST_DISC_HIP=1 (opt-in,
+hiast_amd/switches.py) routes every layer whose input is a float32 device tensor through the library's own 4x4 / stride-2
+kernels instead (HF.disc_conv4x4s2 = hiast_disc_conv_fwd / _dgrad / _wgrad): bias and LeakyReLU in the forward
+epilogue, the activation's backward in the gradient kernels' prologue, fp32 arithmetic also under autocast, and no
+weight-gradient launch when the weights are detached (`params=`)."""
 from torch import nn
 from torch.nn import functional as F
+
+from hiast_amd import switches as SW
 
 __all__ = ["build_discriminator", "FCDiscriminator"]
 
@@ -24,6 +32,11 @@ class FCDiscriminator(nn.Module):
             m = getattr(self, name)
             wgt = m.weight if params is None else params[name + ".weight"]
             b = m.bias if params is None else params[name + ".bias"]
+            if SW.on("HIAST_DISC_HIP"):
+                from hiast_amd import functional as HF
+                if HF.disc_conv_ok(x, wgt):
+                    x = HF.disc_conv4x4s2(x, wgt, b, name != "classifier")
+                    continue
             x = F.conv2d(x, wgt, b, stride=2, padding=1)
             if name != "classifier":
                 x = F.leaky_relu(x, 0.2, inplace=True)

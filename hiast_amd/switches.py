@@ -8,7 +8,10 @@ import os
 _NAMES = ("HIAST_NO_BN_MASK", "HIAST_NO_BN_BWD_FUSION", "HIAST_LIB_WGRAD", "HIAST_NO_WGROUP", "HIAST_NO_XSUM",
           "HIAST_NO_IDT_HANDOFF", "HIAST_LIB_STEM")
 SWITCHES = {n: os.environ.get(n, "0") == "1" for n in _NAMES}
+# opt-IN paths (off unless set to "1"), kept apart from the opt-outs above; read once and flipped by tests the same way
+_OPT_IN_NAMES = ("HIAST_DISC_HIP",)
+OPT_IN = {n: os.environ.get(n, "0") == "1" for n in _OPT_IN_NAMES}
 
 
 def on(name):
-    return SWITCHES[name]
+    return OPT_IN[name] if name in OPT_IN else SWITCHES[name]

@@ -559,6 +559,26 @@ int hiast_dinput_fwd(const float* logits_lr, int mode, float* out, int B, int C,
 int hiast_dinput_bwd(const float* logits_lr, int mode, const float* gout, float* scratch, float* dlogits_lr,
                      int B, int C, int h, int w, int H, int W, hiast_stream_t stream);
 
+/* ---- K19: the discriminator's 4x4 / stride-2 / padding-1 convolutions (adversarial warm-up stage) -----------
+ * sseg/models/modules/discriminator.py:7-33 (FCDiscriminator: nn.Conv2d(kernel_size=4, stride=2, padding=1) x 5 with
+ * LeakyReLU(0.2) between them) and what autograd derives from it.  fp32, contiguous NCHW, fp32 accumulation:
+ *   x [B,Cin,H,W], w [Cout,Cin,4,4], bias [Cout] (NULL = none), y / dy [B,Cout,Ho,Wo], Ho = (H - 2) / 2 + 1, Wo likewise.
+ * fwd:   y = conv(x, w) + bias, then LeakyReLU(0.2) when leaky != 0.
+ * dgrad: dx (overwritten) from dy and w; with leaky != 0, dy is first multiplied by the activation's slope taken from the
+ *        saved OUTPUT y (y > 0 ? 1 : 0.2), i.e. dy is the gradient w.r.t. the activation's output.  y may be NULL when leaky == 0.
+ * wgrad: dw [Cout,Cin,4,4] and db [Cout] (NULL = not wanted), overwritten, from x and the same gated dy.  Pixel ranges are
+ *        summed into workspace partials and added in a fixed order: two calls on the same inputs give the same bits.
+ * workspace: hiast_disc_conv_workspace_bytes(B, Cin, Cout, H, W) bytes (0 = shape refused), 4-byte aligned, private to the
+ *        call until the stream has passed it; one size serves dgrad and wgrad.  It never shrinks when B, H or W grow.
+ * Refused (HIAST_E_RANGE): H or W < 2, more than 4096 channels, a tensor of 2^31 elements or more. */
+size_t hiast_disc_conv_workspace_bytes(int B, int Cin, int Cout, int H, int W);
+int hiast_disc_conv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int H, int W,
+                        int leaky, hiast_stream_t stream);
+int hiast_disc_conv_dgrad(const float* dy, const float* y, const float* w, float* dx, int B, int Cin, int Cout, int H, int W,
+                          int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
+int hiast_disc_conv_wgrad(const float* x, const float* dy, const float* y, float* dw, float* db, int B, int Cin, int Cout,
+                          int H, int W, int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
+
 /* ---- K12: IoU histograms --------------------------------------------------------------
  * utils/metrics.py:6-19 intersectionAndUnionGPU: pred/target int64 [N]; target==255 is
  * ignored; inter/area_pred/area_tgt i64 [K] ACCUMULATED (caller zeroes). */
