@@ -32,6 +32,8 @@ SIGNATURES = {
     "hiast_st_loss_workspace_bytes": (c_sz, [c_int] * 6),
     "hiast_st_loss_fwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 8 + [c_vp, c_vp, c_sz, c_vp]),
     "hiast_st_loss_bwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 8 + [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "hiast_st_loss_cst_fwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 9 + [c_vp, c_vp, c_sz, c_vp]),
+    "hiast_st_loss_cst_bwd": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 9 + [c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "hiast_aspp_wpack_bytes": (c_sz, [c_int, c_int]),
     "hiast_aspp_workspace_bytes": (c_sz, [c_int] * 5),
     "hiast_aspp_pack_weights": (c_int, [c_vp] * 8 + [c_int, c_int, c_vp, c_vp]),

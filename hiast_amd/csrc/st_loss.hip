@@ -12,6 +12,19 @@
 // bwd: per-thread column gradients are folded into low-res cells through LDS in a fixed order,
 //      written as per-block partial tiles, and summed by a combine kernel => no float atomics,
 //      bitwise reproducible.
+//
+// The consistency term (sum slots 3 and 6, coefficient 3) is a compile-time KIND, cfg.cst_training.cst_loss.type of the
+// reference (losses.py:9-41; the trainer hands 'CE' the teacher's arg-max, the others its softmax,
+// consistency_self_training_trainer.py:113-124):
+//   0 SoftCE  -q1_c logp_c                          q1 = softmax(zt) in fp32
+//   1 CE      l = lse(z) - z[argmax zt], per PIXEL; the reference multiplies the [B,H,W] loss by the [B,1,H,W] mask, which
+//             broadcasts to [B,B,H,W] (out[i,j] = l[j] mask[i], losses.py:86-87): per (image, pixel) that is l * M with
+//             M = the number of images of the batch whose mask holds at this pixel position (B label bytes per pixel)
+//   2 KLDIV   q_c (log q_c - logp_c)                q = softmax(q1): LOSS['KLDIV'] applies a softmax to the probabilities
+//                                                   it is handed (losses.py:21-23) — a double softmax, kept
+//   3 MSE     (z_c - q1_c)^2                        on the raw student logits (losses.py:9-13)
+// KIND 0 compiles to the instructions it had before the other kinds existed (its code sits in `if constexpr (KIND == 0)`
+// blocks of its own, untouched).
 #include "common.h"
 
 namespace hiast {
@@ -21,8 +34,23 @@ constexpr int LOSS_THREADS = 256;
 template <typename LT>
 __device__ __forceinline__ int load_label(const LT* p, size_t i) { return (int)p[i]; }
 
+enum { CST_SOFTCE = 0, CST_CE = 1, CST_KLDIV = 2, CST_MSE = 3 };
+
+// CE kind: M = number of images of the batch (gridDim.z of them) whose region mask holds at pixel (Y, X)
+template <typename LT>
+__device__ __forceinline__ int region_count(const LT* plbl, int B, int H, int W, int Y, int X, int region)
+{
+    if (region == 2) return B;
+    int M = 0;
+    for (int bb = 0; bb < B; ++bb) {
+        const bool ig = load_label(plbl, ((size_t)bb * H + Y) * W + X) == HIAST_IGNORE;
+        M += (region == 0 ? ig : !ig) ? 1 : 0;
+    }
+    return M;
+}
+
 // ------------------------------------------------------------------------------------------ fwd
-template <int C, bool TEACHER, typename LT>
+template <int C, bool TEACHER, typename LT, int KIND = CST_SOFTCE>
 __global__ __launch_bounds__(LOSS_THREADS) void st_loss_fwd_kernel(
     const float* __restrict__ zs_lr, const float* __restrict__ zt_lr, const LT* __restrict__ plbl,
     int h, int w, int H, int W, float sh, float sw, int region, double* __restrict__ partial)
@@ -83,35 +111,110 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_fwd_kernel(
                 ++n_ign;
             }
             const bool in_region = TEACHER && (region == 2 || (region == 0 ? ign : !ign));
-            float mt = 0.f, invSt = 0.f;
-            if (TEACHER && in_region) {
+            if constexpr (KIND == CST_SOFTCE) {
+                float mt = 0.f, invSt = 0.f;
+                if (TEACHER && in_region) {
 #pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
-                    mt = (c == 0 || z > mt) ? z : mt;
-                }
-                float St = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) St += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt);
-                invSt = 1.0f / St;
-            }
-            if (ign || in_region) {
-                float e = 0.f, cs = 0.f;
-                int cn = 0;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
-                    if (ign) e -= __expf(logp) * logp;
-                    if (TEACHER && in_region) {
-                        const float q = __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
-                        const float prod = (-logp) * q;        // losses.py:61
-                        cs += prod;
-                        cn += (prod != 0.0f) ? 1 : 0;          // losses.py:89
+                    for (int c = 0; c < C; ++c) {
+                        const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
+                        mt = (c == 0 || z > mt) ? z : mt;
                     }
+                    float St = 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) St += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt);
+                    invSt = 1.0f / St;
                 }
-                a_ent += e;
-                a_cst += cs;
-                n_cst += cn;
+                if (ign || in_region) {
+                    float e = 0.f, cs = 0.f;
+                    int cn = 0;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
+                        if (ign) e -= __expf(logp) * logp;
+                        if (TEACHER && in_region) {
+                            const float q = __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
+                            const float prod = (-logp) * q;        // losses.py:61
+                            cs += prod;
+                            cn += (prod != 0.0f) ? 1 : 0;          // losses.py:89
+                        }
+                    }
+                    a_ent += e;
+                    a_cst += cs;
+                    n_cst += cn;
+                }
+            } else {
+                static_assert(TEACHER, "the CE / KLDIV / MSE consistency kinds need the teacher");
+                if (ign) {
+                    float e = 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
+                        e -= __expf(logp) * logp;
+                    }
+                    a_ent += e;
+                }
+                if constexpr (KIND == CST_CE) {
+                    const int M = region_count(plbl, (int)gridDim.z, H, W, Y, X, region);
+                    if (M > 0) {
+                        float mt = 0.f;
+                        int yt = 0;
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {          // first maximum wins (torch.argmax / torch.max)
+                            const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
+                            const bool up = (c == 0 || z > mt);
+                            mt = up ? z : mt;
+                            yt = up ? c : yt;
+                        }
+                        float zyt = 0.f;
+#pragma unroll
+                        for (int c = 0; c < C; ++c) zyt = (c == yt) ? lerp_v(st[c], sb[c], sy.l0, sy.l1) : zyt;
+                        const float l = lse - zyt;             // losses.py:35, reduction='none'
+                        a_cst += l * (float)M;                 // Σ_i l[j] mask[i], losses.py:86-87
+                        n_cst += (l != 0.0f) ? M : 0;          // losses.py:89
+                    }
+                } else if (in_region) {
+                    float mt = 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
+                        mt = (c == 0 || z > mt) ? z : mt;
+                    }
+                    float St = 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) St += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt);
+                    const float invSt = 1.0f / St;
+                    float cs = 0.f;
+                    int cn = 0;
+                    if constexpr (KIND == CST_KLDIV) {
+                        // q = softmax(q1), q1 in [0, 1]: exp(q1) in [1, e], no shift needed
+                        float S2 = 0.f;
+#pragma unroll
+                        for (int c = 0; c < C; ++c)
+                            S2 += __expf(__expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt);
+                        const float invS2 = 1.0f / S2, logS2 = __logf(S2);
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
+                            const float q1 = __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
+                            const float q = __expf(q1) * invS2;
+                            const float prod = q * ((q1 - logS2) - logp);   // nn.KLDivLoss: q (log q - logp)
+                            cs += prod;
+                            cn += (prod != 0.0f) ? 1 : 0;
+                        }
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            const float z = lerp_v(st[c], sb[c], sy.l0, sy.l1);
+                            const float q1 = __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
+                            const float d = z - q1;
+                            const float prod = d * d;                       // nn.MSELoss on the raw logits
+                            cs += prod;
+                            cn += (prod != 0.0f) ? 1 : 0;
+                        }
+                    }
+                    a_cst += cs;
+                    n_cst += cn;
+                }
             }
         }
     }
@@ -155,7 +258,7 @@ __global__ __launch_bounds__(256) void st_loss_finalize_kernel(const double* __r
 // ------------------------------------------------------------------------------------------ bwd
 // Block = the columns whose left source column x0 lies in cells [i0, i0+TI); partial tile
 // out[b][c][j][r][xb][TI+1], r = 0: contribution to source row j, r = 1: to source row y1(j).
-template <int C, bool TEACHER, typename LT>
+template <int C, bool TEACHER, typename LT, int KIND = CST_SOFTCE>
 __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
     const float* __restrict__ zs_lr, const float* __restrict__ zt_lr, const LT* __restrict__ plbl,
     int h, int w, int H, int W, float sh, float sw, int region, int TI,
@@ -233,18 +336,34 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
                 }
             }
             float mt = 0.f, invSt = 0.f, Q = 0.f;
-            if (TEACHER && in_region) {
+            // KIND 1 (CE): every pixel with M > 0 carries the term, yt = arg-max of the teacher; KIND 2: invS2 / Q of q = softmax(q1)
+            int yt = 0;
+            float wM = 0.f, invS2 = 0.f;
+            if constexpr (KIND == CST_CE) wM = (float)region_count(plbl, (int)gridDim.z, H, W, Y, X, region);
+            if (TEACHER && (KIND == CST_CE ? wM > 0.f : in_region)) {
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
+                    if constexpr (KIND == CST_CE) yt = (c == 0 || z > mt) ? c : yt;
                     mt = (c == 0 || z > mt) ? z : mt;
                 }
                 float St = 0.f;
 #pragma unroll
                 for (int c = 0; c < C; ++c) St += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt);
                 invSt = 1.0f / St;
+                if constexpr (KIND == CST_SOFTCE) {
 #pragma unroll
-                for (int c = 0; c < C; ++c) Q += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
+                    for (int c = 0; c < C; ++c) Q += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
+                }
+                if constexpr (KIND == CST_KLDIV) {
+                    float S2 = 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) S2 += __expf(__expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt);
+                    invS2 = 1.0f / S2;
+#pragma unroll
+                    for (int c = 0; c < C; ++c)
+                        Q += __expf(__expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt) * invS2;
+                }
             }
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -253,11 +372,26 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
                 float g = ign ? 0.f : A1 * (p - (c == y ? 1.f : 0.f));          // CE
                 g += A2 * (wconf * (p - invC));                                  // KLD to uniform
                 g += A3 * (wign * (-p * (logp + Hent)));                         // entropy
-                if (TEACHER) {
-                    const float q = in_region
-                                        ? __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt
-                                        : 0.f;
-                    g += A4 * (wreg * (p * Q - q));                              // soft CE
+                if constexpr (KIND == CST_SOFTCE) {
+                    if (TEACHER) {
+                        const float q = in_region
+                                            ? __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt
+                                            : 0.f;
+                        g += A4 * (wreg * (p * Q - q));                              // soft CE
+                    }
+                } else if constexpr (KIND == CST_CE) {
+                    g += A4 * (wM * (p - (c == yt ? 1.f : 0.f)));                    // CE on the teacher's arg-max, M-fold
+                } else {
+                    const float q1 = in_region
+                                         ? __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt
+                                         : 0.f;
+                    if constexpr (KIND == CST_KLDIV) {
+                        const float q = in_region ? __expf(q1) * invS2 : 0.f;
+                        g += A4 * (wreg * (p * Q - q));                              // KL(softmax(q1) || p)
+                    } else {
+                        const float z = lerp_v(st[c], sb[c], sy.l0, sy.l1);
+                        g += A4 * (wreg * (2.0f * (z - q1)));                        // MSE on the raw logits
+                    }
                 }
                 gt[c] = fmaf(sy.l0, g, gt[c]);      // adjoint of lerp_v
                 gb[c] = fmaf(sy.l1, g, gb[c]);
@@ -376,13 +510,28 @@ static int loss_check(const void* a, const void* l, const void* s, const void* w
         default: return HIAST_E_RANGE;                                            \
     }
 
-extern "C" int hiast_st_loss_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
-                                 int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
-                                 double* sums, void* workspace, size_t workspace_bytes,
-                                 hiast_stream_t stream)
+// cst_kind: 0..3 (HIAST_CST_*); kinds other than SoftCE need the teacher
+static int loss_kind_check(int cst_kind, const float* teacher_lr)
+{
+    if (cst_kind < 0 || cst_kind > 3) return HIAST_E_RANGE;
+    if (cst_kind != 0 && !teacher_lr) return HIAST_E_ARG;
+    return 0;
+}
+
+#define HIAST_LOSS_KINDS(CALL)                                                                     \
+    switch (cst_kind) {                                                                            \
+        case 1: { HIAST_LOSS_DISPATCH(CALL(hiast::CST_CE)) } break;                                \
+        case 2: { HIAST_LOSS_DISPATCH(CALL(hiast::CST_KLDIV)) } break;                             \
+        default: { HIAST_LOSS_DISPATCH(CALL(hiast::CST_MSE)) } break;                              \
+    }
+
+static int loss_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl, int plbl_is_i64, int B,
+                    int C, int h, int w, int H, int W, int region, int cst_kind, double* sums, void* workspace,
+                    size_t workspace_bytes, hiast_stream_t stream)
 {
     int e = loss_check(logits_lr, plbl, sums, workspace, B, C, h, w, H, W, region);
     if (e) return e;
+    if ((e = loss_kind_check(cst_kind, teacher_lr))) return e;
     hiast::LossGeom g;
     if ((e = hiast::loss_geom(h, w, H, W, &g))) return e;
     if (workspace_bytes < hiast_st_loss_workspace_bytes(B, C, h, w, H, W)) return HIAST_E_WS;
@@ -393,26 +542,37 @@ extern "C" int hiast_st_loss_fwd(const float* logits_lr, const float* teacher_lr
 #define FWD(T, LT)                                                                                  \
     hipLaunchKernelGGL((hiast::st_loss_fwd_kernel<CC, T, LT>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
                        logits_lr, teacher_lr, (const LT*)plbl, h, w, H, W, g.sh, g.sw, region, partial)
-    if (teacher_lr) {
+#define FWD_K64(KD)                                                                                          \
+    hipLaunchKernelGGL((hiast::st_loss_fwd_kernel<CC, true, int64_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
+                       logits_lr, teacher_lr, (const int64_t*)plbl, h, w, H, W, g.sh, g.sw, region, partial)
+#define FWD_K8(KD)                                                                                           \
+    hipLaunchKernelGGL((hiast::st_loss_fwd_kernel<CC, true, uint8_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
+                       logits_lr, teacher_lr, (const uint8_t*)plbl, h, w, H, W, g.sh, g.sw, region, partial)
+    if (cst_kind != 0) {
+        if (plbl_is_i64) { HIAST_LOSS_KINDS(FWD_K64) } else { HIAST_LOSS_KINDS(FWD_K8) }
+    } else if (teacher_lr) {
         if (plbl_is_i64) { HIAST_LOSS_DISPATCH(FWD(true, int64_t)) } else { HIAST_LOSS_DISPATCH(FWD(true, uint8_t)) }
     } else {
         if (plbl_is_i64) { HIAST_LOSS_DISPATCH(FWD(false, int64_t)) } else { HIAST_LOSS_DISPATCH(FWD(false, uint8_t)) }
     }
 #undef FWD
+#undef FWD_K64
+#undef FWD_K8
     HIAST_CHECK_LAUNCH();
     hipLaunchKernelGGL(hiast::st_loss_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblk, sums);
     HIAST_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int hiast_st_loss_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
-                                 int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
-                                 const double* sums, const float* coef, float* dlogits_lr,
-                                 void* workspace, size_t workspace_bytes, hiast_stream_t stream)
+static int loss_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl, int plbl_is_i64, int B,
+                    int C, int h, int w, int H, int W, int region, int cst_kind, const double* sums,
+                    const float* coef, float* dlogits_lr, void* workspace, size_t workspace_bytes,
+                    hiast_stream_t stream)
 {
     int e = loss_check(logits_lr, plbl, sums, workspace, B, C, h, w, H, W, region);
     if (e) return e;
     if (!coef || !dlogits_lr) return HIAST_E_ARG;
+    if ((e = loss_kind_check(cst_kind, teacher_lr))) return e;
     hiast::LossGeom g;
     if ((e = hiast::loss_geom(h, w, H, W, &g))) return e;
     if (workspace_bytes < hiast_st_loss_workspace_bytes(B, C, h, w, H, W)) return HIAST_E_WS;
@@ -423,16 +583,64 @@ extern "C" int hiast_st_loss_bwd(const float* logits_lr, const float* teacher_lr
     hipLaunchKernelGGL((hiast::st_loss_bwd_kernel<CC, T, LT>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
                        logits_lr, teacher_lr, (const LT*)plbl, h, w, H, W, g.sh, g.sw, region, g.TI,  \
                        sums, coef, tiles)
-    if (teacher_lr) {
+#define BWD_K64(KD)                                                                                          \
+    hipLaunchKernelGGL((hiast::st_loss_bwd_kernel<CC, true, int64_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
+                       logits_lr, teacher_lr, (const int64_t*)plbl, h, w, H, W, g.sh, g.sw, region, g.TI,     \
+                       sums, coef, tiles)
+#define BWD_K8(KD)                                                                                           \
+    hipLaunchKernelGGL((hiast::st_loss_bwd_kernel<CC, true, uint8_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
+                       logits_lr, teacher_lr, (const uint8_t*)plbl, h, w, H, W, g.sh, g.sw, region, g.TI,     \
+                       sums, coef, tiles)
+    if (cst_kind != 0) {
+        if (plbl_is_i64) { HIAST_LOSS_KINDS(BWD_K64) } else { HIAST_LOSS_KINDS(BWD_K8) }
+    } else if (teacher_lr) {
         if (plbl_is_i64) { HIAST_LOSS_DISPATCH(BWD(true, int64_t)) } else { HIAST_LOSS_DISPATCH(BWD(true, uint8_t)) }
     } else {
         if (plbl_is_i64) { HIAST_LOSS_DISPATCH(BWD(false, int64_t)) } else { HIAST_LOSS_DISPATCH(BWD(false, uint8_t)) }
     }
 #undef BWD
+#undef BWD_K64
+#undef BWD_K8
     HIAST_CHECK_LAUNCH();
     const long long total = (long long)B * C * h * w;
     hipLaunchKernelGGL(hiast::st_loss_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        st, tiles, dlogits_lr, C, h, w, g.TI, g.nxb, total);
     HIAST_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int hiast_st_loss_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                                 int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
+                                 double* sums, void* workspace, size_t workspace_bytes,
+                                 hiast_stream_t stream)
+{
+    return loss_fwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, 0, sums, workspace,
+                    workspace_bytes, stream);
+}
+
+extern "C" int hiast_st_loss_cst_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                                     int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
+                                     int cst_kind, double* sums, void* workspace, size_t workspace_bytes,
+                                     hiast_stream_t stream)
+{
+    return loss_fwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, cst_kind, sums, workspace,
+                    workspace_bytes, stream);
+}
+
+extern "C" int hiast_st_loss_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                                 int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
+                                 const double* sums, const float* coef, float* dlogits_lr,
+                                 void* workspace, size_t workspace_bytes, hiast_stream_t stream)
+{
+    return loss_bwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, 0, sums, coef, dlogits_lr,
+                    workspace, workspace_bytes, stream);
+}
+
+extern "C" int hiast_st_loss_cst_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                                     int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
+                                     int cst_kind, const double* sums, const float* coef, float* dlogits_lr,
+                                     void* workspace, size_t workspace_bytes, hiast_stream_t stream)
+{
+    return loss_bwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, cst_kind, sums, coef,
+                    dlogits_lr, workspace, workspace_bytes, stream);
 }

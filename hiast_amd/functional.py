@@ -113,17 +113,18 @@ class _StLossFn(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, logits_lr, teacher_lr, plbl, H, W, region, w_t, w_k, w_e, w_c):
+    def forward(ctx, logits_lr, teacher_lr, plbl, H, W, region, w_t, w_k, w_e, w_c, cst_kind="SoftCE"):
         logits_lr = logits_lr.contiguous()
         if teacher_lr is not None:
             teacher_lr = teacher_lr.contiguous()
         plbl = plbl.contiguous()
         B, C, h, w = logits_lr.shape
         ws = K.st_loss_workspace(B, C, h, w, H, W, logits_lr.device)
-        sums = K.st_loss_fwd(logits_lr, teacher_lr, plbl, H, W, region, ws)
+        cst_kind = K.CST_KINDS[cst_kind] if teacher_lr is not None else 0       # (no teacher: no consistency term)
+        sums = K.st_loss_fwd(logits_lr, teacher_lr, plbl, H, W, region, ws, cst_kind=cst_kind)
         ctx.save_for_backward(logits_lr, teacher_lr, plbl, sums)
         ctx.ws = ws
-        ctx.args = (H, W, region, w_t, w_k, w_e, w_c)
+        ctx.args = (H, W, region, w_t, w_k, w_e, w_c, cst_kind)
         s = sums.float()      # 0/0 -> NaN exactly like the reference's tensor divisions
         ce = w_t * s[0] / s[4]
         kld = w_k * s[1] / (C * s[4])
@@ -136,17 +137,21 @@ class _StLossFn(torch.autograd.Function):
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_ce, g_kld, g_ent, g_cst, _g_sums):
         logits_lr, teacher_lr, plbl, sums = ctx.saved_tensors
-        H, W, region, w_t, w_k, w_e, w_c = ctx.args
+        H, W, region, w_t, w_k, w_e, w_c, cst_kind = ctx.args
         coef = torch.stack([g_ce * w_t, g_kld * w_k, g_ent * w_e, g_cst * w_c]).float().contiguous()
-        d = K.st_loss_bwd(logits_lr, teacher_lr, plbl, H, W, region, sums, coef, ctx.ws)
-        return (d,) + (None,) * 9
+        d = K.st_loss_bwd(logits_lr, teacher_lr, plbl, H, W, region, sums, coef, ctx.ws, cst_kind=cst_kind)
+        return (d,) + (None,) * 10
 
 
-def st_loss(logits_lr, teacher_lr, plbl, size, region="ignored", w_t=1.0, w_k=0.1, w_e=1.0, w_c=0.5):
+def st_loss(logits_lr, teacher_lr, plbl, size, region="ignored", w_t=1.0, w_k=0.1, w_e=1.0, w_c=0.5, cst_kind="SoftCE"):
     """-> (ce, kld, ent, cst) 0-dim tensors, already multiplied by their weights.
-    `teacher_lr` are the teacher's LOW-RES logits (or None); plbl uint8/int64 [B,H,W]."""
+    `teacher_lr` are the teacher's LOW-RES logits (or None); plbl uint8/int64 [B,H,W].
+    `cst_kind`: the consistency term, a name of kernels.CST_KINDS ('SoftCE', 'CE', 'KLDIV', 'MSE' =
+    cfg.cst_training.cst_loss.type); arg-max / softmax of the teacher happen in the kernel."""
+    if cst_kind not in K.CST_KINDS:
+        raise ValueError("cst_kind %r: one of %s" % (cst_kind, ", ".join(K.CST_KINDS)))
     ce, kld, ent, cst, _ = _StLossFn.apply(logits_lr, teacher_lr, plbl, int(size[0]), int(size[1]), region,
-                                            float(w_t), float(w_k), float(w_e), float(w_c))
+                                            float(w_t), float(w_k), float(w_e), float(w_c), cst_kind)
     return ce, kld, ent, cst
 
 

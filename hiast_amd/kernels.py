@@ -299,6 +299,8 @@ def dinput_bwd(logits_lr, gout, entropy):
 
 # ------------------------------------------------------------------------------- K5-K8 loss
 REGION = {"ignored": 0, "confident": 1, "all": 2}
+# cfg.cst_training.cst_loss.type -> the consistency kind of the fused loss (HIAST_CST_* of include/hiast_hip.h)
+CST_KINDS = {"SoftCE": 0, "CE": 1, "KLDIV": 2, "MSE": 3}
 
 
 def _loss_args(logits_lr, teacher_lr, plbl, H, W):
@@ -321,24 +323,42 @@ def st_loss_workspace(B, C, h, w, H, W, device):
     return torch.empty((n + 7) // 8, dtype=torch.float64, device=device)
 
 
-def st_loss_fwd(logits_lr, teacher_lr, plbl, H, W, region, workspace=None):
-    """-> sums f64 [8] (device), see include/hiast_hip.h"""
+def _cst_kind(cst_kind):
+    return CST_KINDS[cst_kind] if isinstance(cst_kind, str) else int(cst_kind)
+
+
+def st_loss_fwd(logits_lr, teacher_lr, plbl, H, W, region, workspace=None, cst_kind=0, cst_entry=False):
+    """-> sums f64 [8] (device), see include/hiast_hip.h.  cst_kind: the consistency term (CST_KINDS name or number);
+    0 goes through hiast_st_loss_fwd unless cst_entry asks for hiast_st_loss_cst_fwd."""
     B, C, h, w = _loss_args(logits_lr, teacher_lr, plbl, H, W)
+    kind = _cst_kind(cst_kind)
     ws = workspace if workspace is not None else st_loss_workspace(B, C, h, w, H, W, logits_lr.device)
     sums = torch.empty(8, dtype=torch.float64, device=logits_lr.device)
+    if kind != 0 or cst_entry:
+        check(_lib.load().hiast_st_loss_cst_fwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
+                                                int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region], kind,
+                                                _ptr(sums), _ptr(ws), ws.numel() * 8, _stream()), "hiast_st_loss_cst_fwd")
+        return sums
     check(_lib.load().hiast_st_loss_fwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
                                         int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region],
                                         _ptr(sums), _ptr(ws), ws.numel() * 8, _stream()), "hiast_st_loss_fwd")
     return sums
 
 
-def st_loss_bwd(logits_lr, teacher_lr, plbl, H, W, region, sums, coef, workspace=None):
+def st_loss_bwd(logits_lr, teacher_lr, plbl, H, W, region, sums, coef, workspace=None, cst_kind=0, cst_entry=False):
     B, C, h, w = _loss_args(logits_lr, teacher_lr, plbl, H, W)
+    kind = _cst_kind(cst_kind)
     _req(sums, torch.float64, 1, "sums")
     _req(coef, torch.float32, 1, "coef")
     assert sums.numel() == 8 and coef.numel() == 4
     ws = workspace if workspace is not None else st_loss_workspace(B, C, h, w, H, W, logits_lr.device)
     d = torch.empty_like(logits_lr)
+    if kind != 0 or cst_entry:
+        check(_lib.load().hiast_st_loss_cst_bwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
+                                                int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region], kind,
+                                                _ptr(sums), _ptr(coef), _ptr(d), _ptr(ws), ws.numel() * 8, _stream()),
+              "hiast_st_loss_cst_bwd")
+        return d
     check(_lib.load().hiast_st_loss_bwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
                                         int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region],
                                         _ptr(sums), _ptr(coef), _ptr(d), _ptr(ws), ws.numel() * 8, _stream()),

@@ -151,7 +151,29 @@ int hiast_tta_fused(const float* const* z, const float* const* zf, const int* hs
  * region: 0 'ignored' (plbl==255), 1 'confident', 2 'all' (losses.py:77-82).
  * teacher_lr may be NULL (no consistency term; s3 = s6 = 0).
  * plbl: uint8 or int64 [B,H,W] (is_i64).
- * workspace: hiast_st_loss_workspace_bytes(...) bytes of scratch. */
+ * workspace: hiast_st_loss_workspace_bytes(...) bytes of scratch.
+ *
+ * The consistency term is pluggable, as cfg.cst_training.cst_loss.type of the reference (losses.py:9-41): the
+ * hiast_st_loss_cst_* entries take cst_kind; hiast_st_loss_fwd / _bwd are their cst_kind = 0 call.  With z the upsampled
+ * student logits, logp their log-softmax, zt the upsampled teacher logits, q1 = softmax(zt) in fp32, slots 3 and 6 hold
+ *   HIAST_CST_SOFTCE 0: s3 = Σ_region Σ_c -q1_c logp_c, s6 = #(non-zero products)                      (as above)
+ *   HIAST_CST_CE     1: l = lse(z) - z[yt] per pixel, yt = arg-max_c zt (the first maximum); s3 = Σ_pixels l M,
+ *                       s6 = Σ_pixels (l != 0 ? M : 0), M = the number of images of the batch whose region mask holds at
+ *                       this pixel position.  This is the reference's behaviour: it multiplies the [B,H,W] per-pixel loss
+ *                       by the [B,1,H,W] mask, which broadcasts to [B,B,H,W] (out[i,j] = l[j] mask[i], losses.py:86-87),
+ *                       so image j contributes wherever M > 0, whether or not its own pixel is in the region.
+ *   HIAST_CST_KLDIV  2: s3 = Σ_region Σ_c q_c (log q_c - logp_c) with q = softmax(q1), s6 = #(non-zero products).  The
+ *                       double softmax is the reference's behaviour: its trainer hands over probabilities and
+ *                       LOSS['KLDIV'] applies a softmax to its target again (losses.py:21-23).
+ *   HIAST_CST_MSE    3: s3 = Σ_region Σ_c (z_c - q1_c)^2 on the RAW student logits (the reference applies no softmax to
+ *                       the student, losses.py:9-13), s6 = #(non-zero squares).
+ * Slots 0-2, 4, 5 do not depend on the kind; the loss is w_c*s3/s6 for every kind.  The gradients of the term are
+ * A4 (p_c Σq1 - q1_c), A4 M (p_c - [c == yt]), A4 (p_c Σq - q_c), A4 2 (z_c - q1_c) with A4 = coef[3] / s6.
+ * cst_kind outside 0..3: HIAST_E_RANGE; a kind other than 0 with teacher_lr == NULL: HIAST_E_ARG (nothing is launched). */
+#define HIAST_CST_SOFTCE 0
+#define HIAST_CST_CE 1
+#define HIAST_CST_KLDIV 2
+#define HIAST_CST_MSE 3
 size_t hiast_st_loss_workspace_bytes(int B, int C, int h, int w, int H, int W);
 int hiast_st_loss_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
                       int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
@@ -164,6 +186,14 @@ int hiast_st_loss_bwd(const float* logits_lr, const float* teacher_lr, const voi
                       int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
                       const double* sums, const float* coef, float* dlogits_lr,
                       void* workspace, size_t workspace_bytes, hiast_stream_t stream);
+/* the same pair with the consistency kind as an argument (HIAST_CST_*, see above) */
+int hiast_st_loss_cst_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                          int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region, int cst_kind,
+                          double* sums, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
+int hiast_st_loss_cst_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                          int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region, int cst_kind,
+                          const double* sums, const float* coef, float* dlogits_lr,
+                          void* workspace, size_t workspace_bytes, hiast_stream_t stream);
 
 /* ---- K1: ASPP head, 4 dilated 3x3 convs summed --------------------------------------
  * ASPP_V2.forward, sseg/models/modules/seg_models/deeplab_v2.py:20-24 (+ autograd):

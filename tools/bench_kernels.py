@@ -156,6 +156,18 @@ def main():
         med, best = timeit(lambda: K.st_loss_bwd(z, zt, pl, H, W, "ignored", sums, coef, ws_))
         byt = B * (3 * C * h * w * 4 + H * W) / 1e9
         print("%-18s B=%d  median %8.3f ms  best %8.3f ms  %7.1f GB/s (algorithmic)" % ("st_loss_bwd", B, med, best, byt / med * 1e3))
+        # the consistency kinds (cst_loss.type) side by side, forward + backward, on the trainer's 65 x 129 head maps
+        hk, wk = h + 1, w + 1
+        z = torch.randn(B, C, hk, wk, device=dev) * 3
+        zt = torch.randn(B, C, hk, wk, device=dev) * 3
+        ws_ = K.st_loss_workspace(B, C, hk, wk, H, W, dev)
+        for kind in K.CST_KINDS:
+            def both(kind=kind):
+                s = K.st_loss_fwd(z, zt, pl, H, W, "ignored", ws_, cst_kind=kind)
+                return K.st_loss_bwd(z, zt, pl, H, W, "ignored", s, coef, ws_, cst_kind=kind)
+            med, best = timeit(both, n=20)
+            print("%-18s B=%d  median %8.3f ms  best %8.3f ms  (fwd + bwd, %dx%d -> %dx%d)" %
+                  ("st_loss[%s]" % kind, B, med, best, hk, wk, H, W))
     if "upsample" in which:
         z = torch.randn(B, C, h, w, device=dev)
         med, best = timeit(lambda: K.upsample_bilinear_ac_fwd(z, H, W))
