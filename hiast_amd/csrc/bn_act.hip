@@ -93,7 +93,14 @@ template <> struct Vec<__half> {
         *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
     }
     static __device__ __forceinline__ float ld1(const __half* p) { return __half2float(*p); }
-    static __device__ __forceinline__ void st1(__half* p, float v) { *p = __float2half_rn(v); }
+    // the fp32 result is pinned in a register before it is converted: left alone, the compiler folds the last multiply / fma
+    // of the scalar kernels into the conversion (v_fma_mixlo_f16: ONE rounding, exact result -> fp16), while store() above
+    // rounds to fp32 and then to fp16 — the two paths then differ in the last fp16 bit of about one element in 4000
+    static __device__ __forceinline__ void st1(__half* p, float v)
+    {
+        asm volatile("" : "+v"(v));
+        *p = __float2half_rn(v);
+    }
 };
 
 __device__ __forceinline__ double block_sum(double v, double* s_red)

@@ -487,11 +487,14 @@ static int bnh_nblk(long long M, int C)
 
 }  // namespace hiast
 
+// the channel counts the kernels are built for: a power of two in [8, 2048] (anything else, 0 included: HIAST_E_RANGE)
+static bool bnh_c_ok(int C) { return C >= 8 && C <= 2048 && (C & (C - 1)) == 0; }
+
 static int bnh_check(const void* x, long long M, int C)
 {
     if (!x) return HIAST_E_ARG;
-    if (M <= 0 || C <= 0) return HIAST_E_ARG;
-    if (C < 8 || C > 2048 || (C & (C - 1)) != 0 || (((uintptr_t)x) & 15)) return HIAST_E_RANGE;
+    if (M <= 0) return HIAST_E_ARG;
+    if (!bnh_c_ok(C) || (((uintptr_t)x) & 15)) return HIAST_E_RANGE;
     return 0;
 }
 
@@ -529,8 +532,8 @@ extern "C" int hiast_bn_nhwc_stats_from_partial(const float* partial, int nblk, 
                                                 hiast_stream_t stream)
 {
     if (!partial || !sums) return HIAST_E_ARG;
-    if (nblk <= 0 || C <= 0) return HIAST_E_ARG;
-    if (C % 8 != 0) return HIAST_E_RANGE;
+    if (nblk <= 0) return HIAST_E_ARG;
+    if (!bnh_c_ok(C)) return HIAST_E_RANGE;
     hipLaunchKernelGGL(hiast::bnh_finalize_kernel, dim3(C * 2 / 16), dim3(256), 0, (hipStream_t)stream, partial, nblk, C,
                        sums);
     HIAST_CHECK_LAUNCH();

@@ -437,7 +437,8 @@ int hiast_conv_wgrad_small_nhwc(const void* dy, const void* x, float* dw, int B,
  * Same arithmetic and passes as K10 (resnet.py:78-98 in train(): batch statistics even with frozen affine
  * parameters, utils/utils.py:60-65) in the layout the convolution kernels of K9c produce / consume.
  * C a power of two in [8, 2048].  sums [C][2] double: (Σx, Σx²) forward, (Σg, Σ g*xhat) backward — all-reduce them
- * across ranks between the stats and the apply call for SyncBN.  workspace: hiast_bn_nhwc_workspace_bytes(C). */
+ * across ranks between the stats and the apply call for SyncBN.  workspace: hiast_bn_nhwc_workspace_bytes(C).
+ * Every entry (hiast_bn_nhwc_stats_from_partial included) refuses any other C, 0 included, with HIAST_E_RANGE. */
 size_t hiast_bn_nhwc_workspace_bytes(int C);
 /* fmt (every call below): HIAST_FMT_BF16 | HIAST_FMT_FP16, the type of the activation tensors x, res, y, dy, dx, dres */
 int hiast_bn_nhwc_stats(const void* x, int64_t M, int C, double* sums, void* workspace, size_t workspace_bytes, int fmt,
