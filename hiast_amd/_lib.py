@@ -105,6 +105,8 @@ SIGNATURES = {
     "hiast_aug2_blur_u8": (c_int, [c_vp] * 5 + [c_int] * 3 + [c_vp]),
     "hiast_adam_prepare": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "hiast_adam_step": (c_int, [c_vp, c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, c_f32, c_f32, c_vp, c_vp]),
+    "hiast_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_int, c_f32, c_f32, c_vp, c_vp]),
+    "hiast_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, c_f32, c_vp, c_vp]),
     "hiast_disc_conv_workspace_bytes": (c_sz, [c_int] * 5),
     "hiast_disc_conv_fwd": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]),
     "hiast_disc_conv_dgrad": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp, c_sz, c_vp]),

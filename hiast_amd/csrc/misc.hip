@@ -1,7 +1,8 @@
-// Version / error strings, K11 (EMA teacher update) and K12 (IoU area histograms).
+// Version / error strings, K11 (EMA teacher update), K12 (IoU area histograms), K13 / K13b / K13c (Adam, SGD, AdamW steps).
 #include <hip/hip_bf16.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "common.h"
 
@@ -100,16 +101,82 @@ __global__ void adam_prepare_kernel(hiast_adam_ctl* __restrict__ ctl, const floa
     ctl->inv_scale = grad_scale ? (float)(1.0 / (double)*grad_scale) : 1.0f;
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(const hiast_adam_rec* __restrict__ table,
-                                                   const int32_t* __restrict__ chunk_tensor,
-                                                   const int64_t* __restrict__ chunk_start, float beta1, float beta2,
-                                                   float omb1, float omb2, float eps, float wd,
-                                                   const hiast_adam_ctl* __restrict__ ctl, double beta1d, double beta2d)
+// One 64Ki-element chunk [s, e) of one tensor for the multi-tensor optimiser steps (K13, K13b, K13c): p updated in place from g
+// and NS state tensors (st0, st1; the unused ones are never dereferenced).  float4 accesses when every pointer in use is
+// 16-byte aligned (s is a multiple of 64Ki), scalar accesses otherwise and for the ragged tail.
+// upd(p, g, s0, s1) is the element rule; it sees registers, the walk does the loads and stores (g is never stored).
+// MISC_NT=1 (A/B build): the state and the gradient are touched once per step — non-temporal, so that the parameters
+// (read next by the EMA update and the weight re-packing) stay in the Infinity Cache
+#ifndef MISC_NT
+#define MISC_NT 0
+#endif
+template <int NS, class F>
+__device__ __forceinline__ void optim_chunk_walk(float* p_, const float* g_, float* st0, float* st1, int64_t s, int64_t e,
+                                                 F upd)
 {
-    const hiast_adam_rec r = table[chunk_tensor[blockIdx.x]];
+    static_assert(NS >= 0 && NS <= 2, "at most two state tensors");
+    uintptr_t bits = ((uintptr_t)p_) | ((uintptr_t)g_);
+    if (NS >= 1) bits |= (uintptr_t)st0;
+    if (NS >= 2) bits |= (uintptr_t)st1;
+    auto one = [&](int64_t i) {
+        float p = p_[i], a = 0.f, b = 0.f;
+        if (NS >= 1) a = st0[i];
+        if (NS >= 2) b = st1[i];
+        upd(p, g_[i], a, b);
+        p_[i] = p;
+        if (NS >= 1) st0[i] = a;
+        if (NS >= 2) st1[i] = b;
+    };
+    if ((bits & 15) == 0) {
+        typedef float f32x4_ __attribute__((ext_vector_type(4)));
+        const int64_t nv = (e - s) / 4;
+        float4* p4 = reinterpret_cast<float4*>(p_ + s);
+        const float4* g4 = reinterpret_cast<const float4*>(g_ + s);
+        float4* a4 = NS >= 1 ? reinterpret_cast<float4*>(st0 + s) : nullptr;
+        float4* b4 = NS >= 2 ? reinterpret_cast<float4*>(st1 + s) : nullptr;
+        auto ld = [](const float4* q) {
+            if (MISC_NT) {
+                const f32x4_ t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_*>(q));
+                return make_float4(t.x, t.y, t.z, t.w);
+            }
+            return *q;
+        };
+        auto st = [](float4* q, const float4& t) {
+            if (MISC_NT) __builtin_nontemporal_store((f32x4_){t.x, t.y, t.z, t.w}, reinterpret_cast<f32x4_*>(q));
+            else *q = t;
+        };
+        for (int64_t i = threadIdx.x; i < nv; i += 256) {
+            float4 p = p4[i], a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+            if (NS >= 1) a = ld(a4 + i);
+            if (NS >= 2) b = ld(b4 + i);
+            const float4 g = ld(g4 + i);
+            upd(p.x, g.x, a.x, b.x); upd(p.y, g.y, a.y, b.y); upd(p.z, g.z, a.z, b.z); upd(p.w, g.w, a.w, b.w);
+            p4[i] = p;
+            if (NS >= 1) st(a4 + i, a);
+            if (NS >= 2) st(b4 + i, b);
+        }
+        for (int64_t i = s + nv * 4 + threadIdx.x; i < e; i += 256) one(i);
+    } else {
+        for (int64_t i = s + threadIdx.x; i < e; i += 256) one(i);
+    }
+}
+
+// DECOUPLED = false: K13, torch.optim.Adam (L2 weight decay folded into the gradient), records hiast_adam_rec.
+// DECOUPLED = true:  K13c, torch.optim.AdamW (utils/utils.py:144 of the reference): the weight decay does not pass
+// through the moments — p = p * (1 - lr*wd) first (the factor travels per tensor in hiast_adamw_rec, formed in double on the
+// host as torch forms it), then Adam's update on the bare gradient.  Everything else — the control block, the bias
+// corrections from step - skipped, the chunk walk — is the same code.
+template <bool DECOUPLED>
+__global__ __launch_bounds__(256) void adam_kernel(
+    const typename std::conditional<DECOUPLED, hiast_adamw_rec, hiast_adam_rec>::type* __restrict__ table,
+    const int32_t* __restrict__ chunk_tensor, const int64_t* __restrict__ chunk_start, float beta1, float beta2, float omb1,
+    float omb2, float eps, float wd, const hiast_adam_ctl* __restrict__ ctl, double beta1d, double beta2d)
+{
+    const auto r = table[chunk_tensor[blockIdx.x]];
     const int64_t s = chunk_start[blockIdx.x];
     const int64_t e = (s + 65536 < r.n) ? s + 65536 : r.n;
-    float bc1 = r.bc1, bc2_sqrt = r.bc2_sqrt, inv_scale = 1.0f;
+    float bc1 = r.bc1, bc2_sqrt = r.bc2_sqrt, inv_scale = 1.0f, decay = 1.0f;
+    if constexpr (DECOUPLED) decay = r.decay;
     if (ctl) {                                // device-side control block: skipped step / loss scale / skipped-step count
         if (ctl->skip != 0.f) return;
         inv_scale = ctl->inv_scale;
@@ -119,49 +186,51 @@ __global__ __launch_bounds__(256) void adam_kernel(const hiast_adam_rec* __restr
         bc2_sqrt = (float)sqrt(1.0 - pow(beta2d, t));
     }
     const float step_size = r.lr / bc1;       // omb1 / omb2 = float(1 - beta) formed in double on the host, as torch does
-    auto upd = [&](float& p, float g, float& m, float& v) {
+    optim_chunk_walk<2>(r.p, r.g, r.m, r.v, s, e, [&](float& p, float g, float& m, float& v) {
         g = g * inv_scale;                    // (x 1.0f is exact: the unscaled path keeps its bits)
-        if (wd != 0.f) g = g + wd * p;
+        if (DECOUPLED) p = p * decay;
+        else if (wd != 0.f) g = g + wd * p;
         m = m + (g - m) * omb1;
         v = v * beta2 + omb2 * g * g;
         const float denom = sqrtf(v) / bc2_sqrt + eps;
         p = p - step_size * (m / denom);
-    };
-    const bool vec = ((((uintptr_t)r.p) | ((uintptr_t)r.g) | ((uintptr_t)r.m) | ((uintptr_t)r.v)) & 15) == 0;
-    if (vec) {
-        const int64_t nv = (e - s) / 4;
-        float4* p4 = reinterpret_cast<float4*>(r.p + s);
-        const float4* g4 = reinterpret_cast<const float4*>(r.g + s);
-        float4* m4 = reinterpret_cast<float4*>(r.m + s);
-        float4* v4 = reinterpret_cast<float4*>(r.v + s);
-        // MISC_NT=1 (A/B build): the moments and the gradient are touched once per step — non-temporal, so that the parameters
-        // (read next by the EMA update and the weight re-packing) stay in the Infinity Cache
-#ifndef MISC_NT
-#define MISC_NT 0
-#endif
-        typedef float f32x4_ __attribute__((ext_vector_type(4)));
-        for (int64_t i = threadIdx.x; i < nv; i += 256) {
-            float4 p = p4[i], m, v, g;
-            if (MISC_NT) {
-                const f32x4_ mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4_*>(m4 + i));
-                const f32x4_ vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4_*>(v4 + i));
-                const f32x4_ gg = __builtin_nontemporal_load(reinterpret_cast<const f32x4_*>(g4 + i));
-                m = make_float4(mm.x, mm.y, mm.z, mm.w); v = make_float4(vv.x, vv.y, vv.z, vv.w); g = make_float4(gg.x, gg.y, gg.z, gg.w);
-            } else {
-                m = m4[i]; v = v4[i]; g = g4[i];
-            }
-            upd(p.x, g.x, m.x, v.x); upd(p.y, g.y, m.y, v.y); upd(p.z, g.z, m.z, v.z); upd(p.w, g.w, m.w, v.w);
-            p4[i] = p;
-            if (MISC_NT) {
-                __builtin_nontemporal_store((f32x4_){m.x, m.y, m.z, m.w}, reinterpret_cast<f32x4_*>(m4 + i));
-                __builtin_nontemporal_store((f32x4_){v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4_*>(v4 + i));
-            } else {
-                m4[i] = m; v4[i] = v;
-            }
-        }
-        for (int64_t i = s + nv * 4 + threadIdx.x; i < e; i += 256) upd(r.p[i], r.g[i], r.m[i], r.v[i]);
+    });
+}
+
+// K13b — SGD step over the whole parameter list in ONE launch (reference: torch.optim.SGD(momentum=0.9,
+// weight_decay=5e-4) built in utils/utils.py:140 and stepped by BaseTrainer.update_model,
+// workflows/trainer/base_trainer.py:127-141).  torch's single-tensor formulas (dampening 0, no Nesterov), in its order:
+//   g' = g + wd*p;  buf = buf*mu + g';  p = p - lr*buf          (momentum 0 — no buffer in the record: p = p - lr*g')
+// The host zero-fills a new momentum buffer, so the first applied step leaves buf = g' (torch: clone).  The control block
+// is K13's: the gradients are multiplied by 1 / scale and an overflow step touches nothing; SGD keeps no step count, so the
+// device's count of skipped steps is all the bookkeeping there is.
+__global__ __launch_bounds__(256) void sgd_kernel(const hiast_sgd_rec* __restrict__ table,
+                                                  const int32_t* __restrict__ chunk_tensor,
+                                                  const int64_t* __restrict__ chunk_start, float mu, float wd,
+                                                  const hiast_adam_ctl* __restrict__ ctl)
+{
+    const hiast_sgd_rec r = table[chunk_tensor[blockIdx.x]];
+    const int64_t s = chunk_start[blockIdx.x];
+    const int64_t e = (s + 65536 < r.n) ? s + 65536 : r.n;
+    float inv_scale = 1.0f;
+    if (ctl) {
+        if (ctl->skip != 0.f) return;
+        inv_scale = ctl->inv_scale;
+    }
+    const float lr = r.lr;
+    if (r.buf) {
+        optim_chunk_walk<1>(r.p, r.g, r.buf, nullptr, s, e, [&](float& p, float g, float& buf, float&) {
+            g = g * inv_scale;
+            if (wd != 0.f) g = g + wd * p;
+            buf = buf * mu + g;
+            p = p - lr * buf;
+        });
     } else {
-        for (int64_t i = s + threadIdx.x; i < e; i += 256) upd(r.p[i], r.g[i], r.m[i], r.v[i]);
+        optim_chunk_walk<0>(r.p, r.g, nullptr, nullptr, s, e, [&](float& p, float g, float&, float&) {
+            g = g * inv_scale;
+            if (wd != 0.f) g = g + wd * p;
+            p = p - lr * g;
+        });
     }
 }
 
@@ -304,9 +373,34 @@ extern "C" int hiast_adam_step(const hiast_adam_rec* table, const int32_t* chunk
 {
     if (!table || !chunk_tensor || !chunk_start) return HIAST_E_ARG;
     if (n_chunks <= 0) return HIAST_E_ARG;
-    hipLaunchKernelGGL(hiast::adam_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor,
+    hipLaunchKernelGGL(hiast::adam_kernel<false>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor,
                        chunk_start, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps,
                        weight_decay, ctl, beta1, beta2);
+    HIAST_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int hiast_adamw_step(const hiast_adamw_rec* table, const int32_t* chunk_tensor, const int64_t* chunk_start,
+                                int n_chunks, double beta1, double beta2, float eps, const hiast_adam_ctl* ctl,
+                                hiast_stream_t stream)
+{
+    if (!table || !chunk_tensor || !chunk_start) return HIAST_E_ARG;
+    if (n_chunks <= 0) return HIAST_E_ARG;
+    hipLaunchKernelGGL(hiast::adam_kernel<true>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor,
+                       chunk_start, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, 0.0f, ctl,
+                       beta1, beta2);
+    HIAST_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int hiast_sgd_step(const hiast_sgd_rec* table, const int32_t* chunk_tensor, const int64_t* chunk_start,
+                              int n_chunks, float momentum, float weight_decay, const hiast_adam_ctl* ctl,
+                              hiast_stream_t stream)
+{
+    if (!table || !chunk_tensor || !chunk_start) return HIAST_E_ARG;
+    if (n_chunks <= 0) return HIAST_E_ARG;
+    hipLaunchKernelGGL(hiast::sgd_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor,
+                       chunk_start, momentum, weight_decay, ctl);
     HIAST_CHECK_LAUNCH();
     return 0;
 }

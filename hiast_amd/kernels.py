@@ -905,6 +905,62 @@ def adam_step(plan, params, grads, exp_avgs, exp_avg_sqs, lrs, bc1s, bc2_sqrts, 
           "hiast_adam_step")
 
 
+# ------------------------------------------------------------------------------- K13b SGD / K13c AdamW
+class SgdPlan(AdamPlan):
+    """AdamPlan's chunk tables with hiast_sgd_rec records (buf = 0: no momentum buffer)"""
+    REC = np.dtype([("p", np.int64), ("g", np.int64), ("buf", np.int64), ("n", np.int64), ("lr", np.float32),
+                    ("pad", np.float32)])
+
+
+class AdamWPlan(AdamPlan):
+    """AdamPlan's chunk tables with hiast_adamw_rec records (hiast_adam_rec + decay)"""
+    REC = np.dtype([("p", np.int64), ("g", np.int64), ("m", np.int64), ("v", np.int64), ("n", np.int64),
+                    ("lr", np.float32), ("bc1", np.float32), ("bc2s", np.float32), ("step", np.float32),
+                    ("decay", np.float32), ("pad", np.float32)])
+
+
+def _optim_check(fn, plan, i, named):
+    for t, nm in named:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == plan.numels[i]):
+            raise ValueError("%s: %s %d must be a contiguous float32 HIP tensor of %d elements" % (fn, nm, i, plan.numels[i]))
+
+
+def sgd_step(plan, params, grads, bufs, lrs, momentum, weight_decay, ctl=None):
+    """torch.optim.SGD (dampening 0, no Nesterov) over all tensors in one launch; p / buf updated in place.  bufs: the
+    momentum buffers (zero-filled when new), or None for momentum 0 (no state is read or written).  With ctl (a control
+    block adam_prepare has filled for this step) the gradients are multiplied by 1 / grad_scale and the whole update is
+    skipped on an overflow — no host synchronisation"""
+    if not isinstance(plan, SgdPlan):
+        raise ValueError("sgd_step: plan must be an SgdPlan")
+    if (bufs is None) != (float(momentum) == 0.0):
+        raise ValueError("sgd_step: momentum buffers go with momentum != 0, and only with it")
+    h = plan.host
+    for i, (p, g) in enumerate(zip(params, grads)):
+        b = None if bufs is None else bufs[i]
+        _optim_check("sgd_step", plan, i, ((p, "param"), (g, "grad")) + (() if b is None else ((b, "momentum_buffer"),)))
+        h[i] = (p.data_ptr(), g.data_ptr(), 0 if b is None else b.data_ptr(), p.numel(), lrs[i], 0.0)
+    h2d_async(h.view(np.uint8).reshape(-1), plan.table.device, out=plan.table)
+    check(_lib.load().hiast_sgd_step(_ptr(plan.table), _ptr(plan.chunk_tensor), _ptr(plan.chunk_start), plan.n_chunks,
+                                     float(momentum), float(weight_decay), _ptr(ctl), _stream()), "hiast_sgd_step")
+
+
+def adamw_step(plan, params, grads, exp_avgs, exp_avg_sqs, lrs, bc1s, bc2_sqrts, beta1, beta2, eps, weight_decay,
+               ctl=None, steps=None):
+    """adam_step with torch.optim.AdamW's decoupled weight decay: p *= float(1 - lr * weight_decay) (the factor formed in
+    double per tensor, as torch forms it) ahead of Adam's update on the bare gradient; ctl / steps as for adam_step"""
+    assert (ctl is None) == (steps is None)
+    if not isinstance(plan, AdamWPlan):
+        raise ValueError("adamw_step: plan must be an AdamWPlan")
+    h = plan.host
+    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+        _optim_check("adamw_step", plan, i, ((p, "param"), (g, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")))
+        h[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lrs[i], bc1s[i], bc2_sqrts[i],
+                0.0 if steps is None else float(steps[i]), 1.0 - float(lrs[i]) * float(weight_decay), 0.0)
+    h2d_async(h.view(np.uint8).reshape(-1), plan.table.device, out=plan.table)
+    check(_lib.load().hiast_adamw_step(_ptr(plan.table), _ptr(plan.chunk_tensor), _ptr(plan.chunk_start), plan.n_chunks,
+                                       float(beta1), float(beta2), float(eps), _ptr(ctl), _stream()), "hiast_adamw_step")
+
+
 # ------------------------------------------------------------------------------- K12 IoU
 def confusion_hist(pred, target, K, inter=None, area_pred=None, area_tgt=None):
     _req(pred, torch.int64, None, "pred")

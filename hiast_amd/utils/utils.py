@@ -250,13 +250,103 @@ class FusedAdam(torch.optim.Optimizer):
             plan = self._plan.get(len(ps)) if isinstance(self._plan, dict) else None
             numels = tuple(p.numel() for p in ps)
             if plan is None or plan.numels != numels:
-                plan = K.AdamPlan(numels, ps[0].device)
+                plan = self._new_plan(K, numels, ps[0].device)
                 self._plan = dict(self._plan or {})
                 self._plan[len(ps)] = plan
             one = [1.0] * len(ps)       # bias corrections: formed on the device from (attempted - skipped) steps
-            K.adam_step(plan, [p.data for p in ps], [p.grad.contiguous() for p in ps], [st["exp_avg"] for _, _, st in items],
-                        [st["exp_avg_sq"] for _, _, st in items], [lr for _, lr, _ in items], one, one, betas[0], betas[1],
-                        eps, wd, ctl=self._ctl, steps=[float(st["step"]) for _, _, st in items])
+            self._launch(K)(plan, [p.data for p in ps], [p.grad.contiguous() for p in ps],
+                            [st["exp_avg"] for _, _, st in items], [st["exp_avg_sq"] for _, _, st in items],
+                            [lr for _, lr, _ in items], one, one, betas[0], betas[1], eps, wd, ctl=self._ctl,
+                            steps=[float(st["step"]) for _, _, st in items])
+            # raw-pointer writes do not move Parameter._version by themselves; the packed-weight caches key on it
+            torch.autograd.graph.increment_version(ps)
+        return loss
+
+    # the two places where the weight-decay rule shows: the record layout and the entry point (FusedAdamW overrides them)
+    @staticmethod
+    def _new_plan(K, numels, device):
+        return K.AdamPlan(numels, device)
+
+    @staticmethod
+    def _launch(K):
+        return K.adam_step
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW (decoupled weight decay, no amsgrad) in ONE HIP launch (hiast_adamw_step): FusedAdam — its state
+    layout, its device-side handling of the loss scale, its counting of applied steps — with the other weight-decay rule:
+    p *= 1 - lr*wd ahead of Adam's update on the bare gradient, instead of g += wd*p."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    @staticmethod
+    def _new_plan(K, numels, device):
+        return K.AdamWPlan(numels, device)
+
+    @staticmethod
+    def _launch(K):
+        return K.adamw_step
+
+
+class FusedSGD(torch.optim.Optimizer):
+    """torch.optim.SGD (momentum, L2 weight decay; no dampening, no Nesterov) whose step is ONE HIP launch over every
+    parameter (hiast_sgd_step).  Same param_groups / state layout ('momentum_buffer'), so LR schedulers and checkpoints
+    are interchangeable.  As with FusedAdam the loss scaler's decision is taken on the device: scaler.step(opt) hands
+    over `grad_scale` / `found_inf`, the kernel unscales the gradients and leaves parameters and buffers alone on an
+    overflow, and the host never reads found_inf.  SGD keeps no step count, so a skipped step needs no bookkeeping."""
+    _step_supports_amp_scaling = True
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+        if dampening != 0 or nesterov:
+            raise ValueError("FusedSGD implements dampening=0, nesterov=False only (got dampening=%r, nesterov=%r)"
+                             % (dampening, nesterov))
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=False))
+        self._plan = {}
+        self._ctl = None
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from hiast_amd import kernels as K
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        by_hyper = {}
+        for group in self.param_groups:
+            if group["dampening"] != 0 or group["nesterov"]:
+                raise ValueError("FusedSGD implements dampening=0, nesterov=False only")
+            key = (group["momentum"], group["weight_decay"])
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                buf = None
+                if group["momentum"] != 0:      # (momentum 0 keeps no state at all, as in torch)
+                    buf = self.state[p].get("momentum_buffer")
+                    if buf is None:
+                        # zero, not a clone of the gradient: the kernel's first applied step leaves buf = g', and a step
+                        # the device skips (overflow) leaves it zero, as torch leaves it absent
+                        buf = self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                by_hyper.setdefault(key, []).append((p, group["lr"], buf))
+        dev = next((p.device for items in by_hyper.values() for p, _, _ in items), None)
+        if dev is None:
+            return loss
+        ctl = None
+        if grad_scale is not None or found_inf is not None:
+            if self._ctl is None:
+                self._ctl = torch.zeros(8, dtype=torch.float32, device=dev)
+            ctl = self._ctl
+            K.adam_prepare(ctl, grad_scale, found_inf)        # ONE decision per step, shared by every launch below
+        for (momentum, wd), items in by_hyper.items():
+            ps = [p for p, _, _ in items]
+            numels = tuple(p.numel() for p in ps)
+            plan = self._plan.get((momentum, wd))
+            if plan is None or plan.numels != numels:
+                plan = self._plan[(momentum, wd)] = K.SgdPlan(numels, ps[0].device)
+            K.sgd_step(plan, [p.data for p in ps], [p.grad.contiguous() for p in ps],
+                       [buf for _, _, buf in items] if momentum != 0 else None,
+                       [lr for _, lr, _ in items], momentum, wd, ctl=ctl)
             # raw-pointer writes do not move Parameter._version by themselves; the packed-weight caches key on it
             torch.autograd.graph.increment_version(ps)
         return loss
@@ -268,13 +358,15 @@ def init_optimizers(cfg, model):
     groups = _unwrap(model).seg_model.get_optimizer_params(cfg.train.lr)
     groups = [{"params": [p for p in g["params"] if p.requires_grad], "lr": g["lr"]} for g in groups]
     kind = cfg.train.optimizer
+    # HIAST_TORCH_OPTIM=1 (A/B runs): torch's SGD / AdamW on the device as well, as before the fused steps existed
+    fused = all(p.is_cuda for g in groups for p in g["params"]) and os.environ.get("HIAST_TORCH_OPTIM", "0") != "1"
     if kind == "SGD":
-        opt = torch.optim.SGD(groups, momentum=0.9, weight_decay=0.0005)
+        opt = (FusedSGD if fused else torch.optim.SGD)(groups, momentum=0.9, weight_decay=0.0005)
     elif kind == "Adam":
         on_device = all(p.is_cuda for g in groups for p in g["params"])
         opt = (FusedAdam if on_device else torch.optim.Adam)(groups, betas=(0.9, 0.999), weight_decay=0.0005)
     elif kind == "AdamW":
-        opt = torch.optim.AdamW(groups, betas=(0.9, 0.999), weight_decay=0.0005)
+        opt = (FusedAdamW if fused else torch.optim.AdamW)(groups, betas=(0.9, 0.999), weight_decay=0.0005)
     else:
         raise ValueError("%s is not a valid optimizer" % kind)
     d_opt = None

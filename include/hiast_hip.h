@@ -579,6 +579,31 @@ int hiast_adam_step(const hiast_adam_rec* table, const int32_t* chunk_tensor, co
                     int n_chunks, double beta1, double beta2, float eps, float weight_decay, const hiast_adam_ctl* ctl,
                     hiast_stream_t stream);
 
+/* ---- K13b: SGD step ----------------------------------------------------------------------
+ * torch.optim.SGD(momentum, dampening=0, nesterov=False, weight_decay) as built by utils/utils.py:140 (momentum 0.9,
+ * weight decay 5e-4: the DeepLab-V2 warm-up recipe) and stepped by BaseTrainer.update_model (base_trainer.py:127-141):
+ * every parameter tensor in ONE launch, torch's single-tensor formulas in its operation order, fp32, no contraction:
+ *   g' = g * inv_scale;  if (wd != 0) g' = g' + wd * p;
+ *   buf != NULL:  buf = buf * momentum + g';  p = p - lr * buf          buf == NULL (momentum 0):  p = p - lr * g'
+ * table: device array of records {p, g, buf (momentum_buffer or NULL: no state is read or written), n, lr}; chunk tables
+ * as for K11.  A new momentum buffer is zero-filled by the host: the first applied step leaves buf = g' (torch clones).
+ * ctl (may be NULL): K13's control block, filled by hiast_adam_prepare once per optimiser step: inv_scale multiplies
+ * every gradient, and with ctl->skip != 0 the launch returns before touching anything (SGD keeps no step count). */
+typedef struct { float* p; const float* g; float* buf; int64_t n; float lr; float pad; } hiast_sgd_rec;
+int hiast_sgd_step(const hiast_sgd_rec* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int n_chunks,
+                   float momentum, float weight_decay, const hiast_adam_ctl* ctl, hiast_stream_t stream);
+
+/* ---- K13c: AdamW step --------------------------------------------------------------------
+ * torch.optim.AdamW(betas, eps, weight_decay) as built by utils/utils.py:144: K13 with DECOUPLED weight decay — the same
+ * kernel body, instantiated with the other rule:
+ *   g' = g * inv_scale;  p = p * decay;  m = m + (g' - m)*(1 - b1);  v = v*b2 + (1 - b2)*g'*g';
+ *   p  = p - (lr / bc1) * (m / (sqrt(v) / bc2_sqrt + eps))
+ * The record is hiast_adam_rec plus decay = float(1 - lr * weight_decay), formed in double on the host per tensor as
+ * torch forms it (so the entry takes no weight_decay).  bc1 / bc2_sqrt / step and ctl: as for hiast_adam_step. */
+typedef struct { float* p; const float* g; float* m; float* v; int64_t n; float lr; float bc1; float bc2_sqrt; float step; float decay; float pad; } hiast_adamw_rec;
+int hiast_adamw_step(const hiast_adamw_rec* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int n_chunks,
+                     double beta1, double beta2, float eps, const hiast_adam_ctl* ctl, hiast_stream_t stream);
+
 /* ---- K15: discriminator input map (adversarial warm-up stage) -----------------------------
  * sseg/models/segmentors/adversarial_warmup_segmentor.py: F.interpolate(logits, size, bilinear,
  * align_corners=True) :36,:41 followed by D_preprocess_fun :26-29 — mode 0 = softmax(dim=1)
