@@ -111,6 +111,9 @@ SIGNATURES = {
     "hiast_disc_conv_fwd": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]),
     "hiast_disc_conv_dgrad": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp, c_sz, c_vp]),
     "hiast_disc_conv_wgrad": (c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp, c_sz, c_vp]),
+    "hiast_disc_conv16_fwd": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
+    "hiast_disc_conv16_dgrad": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp, c_sz, c_vp]),
+    "hiast_disc_conv16_wgrad": (c_int, [c_vp] * 5 + [c_int] * 7 + [c_vp, c_sz, c_vp]),
     "hiast_confusion_hist": (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_vp]),
 }
 

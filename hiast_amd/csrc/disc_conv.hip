@@ -11,6 +11,8 @@
 // tail of a tile, the tail of K) WITHOUT forming the address, so odd H / W, Cin = 19 / 9 / 2 and Cout = 1 need no special case.
 // The LeakyReLU backward is the prologue of dgrad and wgrad: g = dy * (y > 0 ? 1 : 0.2) from the saved OUTPUT y (slope > 0:
 // sign(y) = sign of the pre-activation; y == 0 takes 0.2, as at::leaky_relu_backward does).
+// hiast_disc_conv16_*: the same three operations with the operands rounded to fp16 / bf16 on the matrix cores, a second tile
+// kernel (dc_gemm16_kernel, below) over the same loaders and stores.
 #include "common.h"
 
 namespace hiast {
@@ -278,6 +280,130 @@ __global__ __launch_bounds__(256) void dc_gemm_kernel(const Op op)
         for (int i = 0; i < 4; ++i) op.store(z, m0 + tx * 4 + i, n0 + ty * 4 + j, tot[i][j] + acc[i][j]);
 }
 
+// ------------------------------------------------------------------------------- the 16-bit matrix-core tile kernel
+// The same three Ops, the same 64 x 64 block on 256 threads, the same two LDS buffers and one barrier per step; the arithmetic
+// is v_mfma_f32_16x16x32_{f16,bf16}: every fetched fp32 value (in the backward: the fp32 gate product) is rounded to the 16-bit
+// type (nearest even; an fp16 overflow becomes inf) when it goes to LDS, products are summed in fp32.  K advances 32 per step
+// = two fetches (k0, k0 + 16); a range whose length is an odd multiple of 16 ends in a half step of zeros.
+//
+// LDS: [row][32 positions] of 16-bit values, a row = 64 B of data in DLD16 * 2 = 96 B.  The sum over k does not care about
+// the order of k as long as both operands agree, so k = 16 kh + kl (kh = which fetch) sits at position
+//     p(k) = 8 (kl & 3) + 4 kh + (kl >> 2)
+// for both tiles.  A non-KFAST thread (row = tid % 64, kl = tid / 64 + 4 i) then owns the eight positions 8 (tid / 64) .. + 7
+// of its row: one 16-byte store instead of eight 2-byte ones.  A KFAST thread (kl = tid % 16, rows tid / 16 + 16 i) stores 2
+// bytes at p and p + 4.  Lane l of a wave reads positions 8 (l >> 4) .. + 7 of row (l & 15) as one 16-byte fragment.
+// Banks with rows 24 dwords apart:
+//   fragment read (ds_read_b128, 16-lane groups {0-3, 12-15, 20-27}, ...; 16-byte slot = 6 row + (l >> 4) mod 16): the
+//       rows 0-3, 12-15 of one quarter give the even slots 0 6 12 2 | 8 14 4 10, rows 4-11 of the next quarter the odd
+//       slots 9 15 5 11 1 7 13 3 (the other groups likewise): conflict-free;
+//   16-byte store (8-lane groups, 32 banks): rows r .. r + 7 at 24 r mod 32 = 0 24 16 8 0 ...: 2-way;
+//   2-byte store (32-lane halves: rows r, r + 1, kl = 0 .. 15 at dwords 4 (kl & 3) + (kl >> 3) = 0 1 4 5 8 9 12 13, two
+//       lanes per dword): row r + 1 at + 24 meets row r in 4 of the 8 dwords: 2-way.
+// (64-byte rows would put a group's fragments on 4 slots: 4-way; 80-byte rows make the 16-byte store conflict-free and the
+// fragment read 2-way — the reads are the larger number.)
+//
+// Orientation: in all three Ops M is the index that is contiguous (or stride 2) in memory, so the M tile is the MFMA's B
+// operand and the N tile its A operand: D[n][m] has m = lane & 15 on the lanes and n = 4 (lane >> 4) + reg in the registers,
+// and the 16 lanes of a group store 16 neighbouring m.  Wave w owns the quadrant m 32 (w & 1) .. + 31, n 32 (w >> 1) .. + 31
+// as 2 x 2 MFMA tiles.  Every 4 steps (128 terms, as DFLUSH x DK above) the accumulators are added into a second level.
+constexpr int DK16 = 2 * DK;      // K step of the 16-bit kernel
+constexpr int DFLUSH16 = DFLUSH / 2;
+constexpr int DLD16 = 48;         // LDS row stride in 16-bit values (96 B)
+
+template <bool F16, bool KFAST>
+__device__ __forceinline__ void dc_put16(unsigned short (*S)[DLD16], int tid, const float r0[4], const float r1[4])
+{
+    typedef H16<F16> HT;
+    if (KFAST) {
+        const int kl = tid & 15, p = 8 * (kl & 3) + (kl >> 2);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            S[(tid >> 4) + 16 * i][p] = HT::enc(r0[i]);
+            S[(tid >> 4) + 16 * i][p + 4] = HT::enc(r1[i]);
+        }
+    } else {
+        *reinterpret_cast<uint4*>(&S[tid & 63][8 * (tid >> 6)]) =
+            make_uint4(HT::pack(r0[0], r0[1]), HT::pack(r0[2], r0[3]), HT::pack(r1[0], r1[1]), HT::pack(r1[2], r1[3]));
+    }
+}
+
+template <class Op, bool F16>
+__global__ __launch_bounds__(256) void dc_gemm16_kernel(const Op op)
+{
+    typedef H16<F16> HT;
+    __shared__ __attribute__((aligned(16))) unsigned short Ms[2][DT][DLD16];
+    __shared__ __attribute__((aligned(16))) unsigned short Ns[2][DT][DLD16];
+    const int tid = (int)threadIdx.x, z = (int)blockIdx.z;
+    const int m0 = (int)blockIdx.x * DT, n0 = (int)blockIdx.y * DT;
+    if (m0 >= op.mrows(z)) return;                   // block-uniform, as above
+    int kb, ke;
+    op.krange(z, kb, ke);
+    const typename Op::Ctx ctx(op, z, m0, n0, tid);
+    const int lane = tid & 63, fr = lane & 15, fq = lane >> 4;
+    const int wm = ((tid >> 6) & 1) * 32, wn = (tid >> 7) * 32;
+    h_f32x4 acc[2][2], tot[2][2];                    // [n tile][m tile]
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) acc[u][t] = tot[u][t] = (h_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+    int step = 0;
+    float ra[2][4], rb[2][4];
+    if (kb < ke) {
+        ctx.fetch(kb, ke, ra[0], rb[0]);
+        ctx.fetch(kb + DK, ke, ra[1], rb[1]);        // past ke: zeros, no address formed
+    }
+    int buf = 0;
+    for (int k0 = kb; k0 < ke; k0 += DK16) {
+        dc_put16<F16, Op::A_KFAST>(Ms[buf], tid, ra[0], ra[1]);
+        dc_put16<F16, Op::B_KFAST>(Ns[buf], tid, rb[0], rb[1]);
+        __syncthreads();                             // one barrier per step, as in dc_gemm_kernel
+        if (k0 + DK16 < ke) {
+            ctx.fetch(k0 + DK16, ke, ra[0], rb[0]);
+            ctx.fetch(k0 + DK16 + DK, ke, ra[1], rb[1]);
+        }
+        uint4 fm[2], fn[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            fm[t] = *reinterpret_cast<const uint4*>(&Ms[buf][wm + 16 * t + fr][8 * fq]);
+            fn[t] = *reinterpret_cast<const uint4*>(&Ns[buf][wn + 16 * t + fr][8 * fq]);
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) acc[u][t] = HT::mfma16(fn[u], fm[t], acc[u][t]);
+        buf ^= 1;
+        if (++step == DFLUSH16) {
+            step = 0;
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    tot[u][t] += acc[u][t];
+                    acc[u][t] = (h_f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+                }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const h_f32x4 v = tot[u][t] + acc[u][t];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) op.store(z, m0 + wm + 16 * t + fr, n0 + wn + 16 * u + 4 * fq + r, v[r]);
+        }
+}
+
+// fmt = 0: the fp32 kernel; HIAST_FMT_FP16 / HIAST_FMT_BF16: the matrix-core kernel in that operand type
+template <class Op>
+void dc_launch(int fmt, dim3 grid, hipStream_t st, const Op& op)
+{
+    if (fmt == HIAST_FMT_FP16) hipLaunchKernelGGL((dc_gemm16_kernel<Op, true>), grid, dim3(256), 0, st, op);
+    else if (fmt == HIAST_FMT_BF16) hipLaunchKernelGGL((dc_gemm16_kernel<Op, false>), grid, dim3(256), 0, st, op);
+    else hipLaunchKernelGGL(dc_gemm_kernel<Op>, grid, dim3(256), 0, st, op);
+}
+
+inline bool dc_fmt16_ok(int fmt) { return fmt == HIAST_FMT_FP16 || fmt == HIAST_FMT_BF16; }
+
 // ----------------------------------------------------------------------------------------------------------- host side
 struct DcPlan {
     int ok;
@@ -324,8 +450,9 @@ extern "C" size_t hiast_disc_conv_workspace_bytes(int B, int Cin, int Cout, int 
     return p.ok ? p.bytes : 0;
 }
 
-extern "C" int hiast_disc_conv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout,
-                                   int H, int W, int leaky, hiast_stream_t stream)
+// the three operations; fmt = 0 (fp32) or a checked 16-bit format
+static int dc_fwd(int fmt, const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int H, int W,
+                  int leaky, hiast_stream_t stream)
 {
     if (!x || !w || !y) return HIAST_E_ARG;
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return HIAST_E_ARG;
@@ -338,13 +465,13 @@ extern "C" int hiast_disc_conv_fwd(const float* x, const float* w, const float* 
     op.K = Cin * 16;
     op.leaky = leaky != 0;
     const dim3 grid((unsigned)((op.M + DT - 1) / DT), (unsigned)((Cout + DT - 1) / DT), 1);
-    hipLaunchKernelGGL(dc_gemm_kernel<FwdOp>, grid, dim3(256), 0, (hipStream_t)stream, op);
+    dc_launch(fmt, grid, (hipStream_t)stream, op);
     HIAST_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int hiast_disc_conv_dgrad(const float* dy, const float* y, const float* w, float* dx, int B, int Cin, int Cout,
-                                     int H, int W, int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream)
+static int dc_dgrad(int fmt, const float* dy, const float* y, const float* w, float* dx, int B, int Cin, int Cout, int H, int W,
+                    int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream)
 {
     if (!dy || !w || !dx || !workspace || (leaky && !y)) return HIAST_E_ARG;
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return HIAST_E_ARG;
@@ -365,14 +492,13 @@ extern "C" int hiast_disc_conv_dgrad(const float* dy, const float* y, const floa
     op.leaky = leaky != 0;
     const int Mc = B * ((H + 1) / 2) * ((W + 1) / 2);        // the largest class (ph = pw = 0)
     const dim3 grid((unsigned)((Mc + DT - 1) / DT), (unsigned)((Cin + DT - 1) / DT), 4);
-    hipLaunchKernelGGL(dc_gemm_kernel<DgradOp>, grid, dim3(256), 0, st, op);
+    dc_launch(fmt, grid, st, op);
     HIAST_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int hiast_disc_conv_wgrad(const float* x, const float* dy, const float* y, float* dw, float* db, int B, int Cin,
-                                     int Cout, int H, int W, int leaky, void* workspace, size_t workspace_bytes,
-                                     hiast_stream_t stream)
+static int dc_wgrad(int fmt, const float* x, const float* dy, const float* y, float* dw, float* db, int B, int Cin, int Cout,
+                    int H, int W, int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream)
 {
     if (!x || !dy || !dw || !workspace || (leaky && !y)) return HIAST_E_ARG;
     if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return HIAST_E_ARG;
@@ -389,11 +515,53 @@ extern "C" int hiast_disc_conv_wgrad(const float* x, const float* dy, const floa
     op.kper = p.kper;
     op.leaky = leaky != 0;
     const dim3 grid((unsigned)((Cout + DT - 1) / DT), (unsigned)((op.N + DT - 1) / DT), (unsigned)p.nsplit);
-    hipLaunchKernelGGL(dc_gemm_kernel<WgradOp>, grid, dim3(256), 0, st, op);
+    dc_launch(fmt, grid, st, op);
     HIAST_CHECK_LAUNCH();
     const long long total = (long long)op.N * Cout;
     hipLaunchKernelGGL(dc_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
                        (const float*)workspace, dw, db, op.N, Cout, p.nsplit);
     HIAST_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int hiast_disc_conv_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout,
+                                   int H, int W, int leaky, hiast_stream_t stream)
+{
+    return dc_fwd(0, x, w, bias, y, B, Cin, Cout, H, W, leaky, stream);
+}
+
+extern "C" int hiast_disc_conv_dgrad(const float* dy, const float* y, const float* w, float* dx, int B, int Cin, int Cout,
+                                     int H, int W, int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream)
+{
+    return dc_dgrad(0, dy, y, w, dx, B, Cin, Cout, H, W, leaky, workspace, workspace_bytes, stream);
+}
+
+extern "C" int hiast_disc_conv_wgrad(const float* x, const float* dy, const float* y, float* dw, float* db, int B, int Cin,
+                                     int Cout, int H, int W, int leaky, void* workspace, size_t workspace_bytes,
+                                     hiast_stream_t stream)
+{
+    return dc_wgrad(0, x, dy, y, dw, db, B, Cin, Cout, H, W, leaky, workspace, workspace_bytes, stream);
+}
+
+extern "C" int hiast_disc_conv16_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout,
+                                     int H, int W, int leaky, int fmt, hiast_stream_t stream)
+{
+    if (!dc_fmt16_ok(fmt)) return HIAST_E_ARG;
+    return dc_fwd(fmt, x, w, bias, y, B, Cin, Cout, H, W, leaky, stream);
+}
+
+extern "C" int hiast_disc_conv16_dgrad(const float* dy, const float* y, const float* w, float* dx, int B, int Cin, int Cout,
+                                       int H, int W, int leaky, int fmt, void* workspace, size_t workspace_bytes,
+                                       hiast_stream_t stream)
+{
+    if (!dc_fmt16_ok(fmt)) return HIAST_E_ARG;
+    return dc_dgrad(fmt, dy, y, w, dx, B, Cin, Cout, H, W, leaky, workspace, workspace_bytes, stream);
+}
+
+extern "C" int hiast_disc_conv16_wgrad(const float* x, const float* dy, const float* y, float* dw, float* db, int B, int Cin,
+                                       int Cout, int H, int W, int leaky, int fmt, void* workspace, size_t workspace_bytes,
+                                       hiast_stream_t stream)
+{
+    if (!dc_fmt16_ok(fmt)) return HIAST_E_ARG;
+    return dc_wgrad(fmt, x, dy, y, dw, db, B, Cin, Cout, H, W, leaky, workspace, workspace_bytes, stream);
 }

@@ -183,16 +183,17 @@ class _DiscConvFn(torch.autograd.Function):
     """one layer of the warm-up discriminator on the library's own kernels (K19): 4x4 / stride 2 / padding 1 convolution +
     bias (+ LeakyReLU 0.2) in one launch; the backward takes the activation's gate from the saved output inside the
     input- and weight-gradient kernels.  The weight-gradient launch is skipped when neither weight nor bias wants a gradient
-    (the `params=` path of FCDiscriminator with detached weights)."""
+    (the `params=` path of FCDiscriminator with detached weights).  fmt = None: the fp32 kernels; torch.float16 /
+    torch.bfloat16: the matrix-core kernels with operands rounded to that type (tensors, saved ones included, stay fp32)."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, x, weight, bias, leaky):
+    def forward(ctx, x, weight, bias, leaky, fmt=None):
         x, weight = x.contiguous(), weight.contiguous()
         bias = bias.contiguous() if bias is not None else None
-        y = K.disc_conv_fwd(x, weight, bias, leaky)
+        y = K.disc_conv_fwd(x, weight, bias, leaky) if fmt is None else K.disc_conv16_fwd(x, weight, bias, leaky, fmt)
         ctx.save_for_backward(x, weight, y)
-        ctx.leaky, ctx.has_bias = leaky, bias is not None
+        ctx.leaky, ctx.has_bias, ctx.fmt = leaky, bias is not None, fmt
         return y
 
     @staticmethod
@@ -201,11 +202,17 @@ class _DiscConvFn(torch.autograd.Function):
         x, weight, y = ctx.saved_tensors
         dy = dy.float().contiguous()
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        dx = K.disc_conv_dgrad(dy, y, weight, x.shape, ctx.leaky) if need_x else None
+        fmt = ctx.fmt
+        dx = None
+        if need_x:
+            dx = (K.disc_conv_dgrad(dy, y, weight, x.shape, ctx.leaky) if fmt is None
+                  else K.disc_conv16_dgrad(dy, y, weight, x.shape, ctx.leaky, fmt))
         dw = db = None
         if need_w or (need_b and ctx.has_bias):
-            dw, db = K.disc_conv_wgrad(x, dy, y, ctx.leaky, want_bias=need_b and ctx.has_bias)
-        return dx, (dw if need_w else None), (db if need_b else None), None
+            want_bias = need_b and ctx.has_bias
+            dw, db = (K.disc_conv_wgrad(x, dy, y, ctx.leaky, want_bias=want_bias) if fmt is None
+                      else K.disc_conv16_wgrad(x, dy, y, ctx.leaky, fmt, want_bias=want_bias))
+        return dx, (dw if need_w else None), (db if need_b else None), None, None
 
 
 def disc_conv_shapes_ok(x_shape, w_shape):
@@ -228,9 +235,15 @@ def disc_conv_ok(x, weight):
             and disc_conv_shapes_ok(x.shape, weight.shape))
 
 
-def disc_conv4x4s2(x, weight, bias, leaky):
-    """leaky_relu?(F.conv2d(x, weight, bias, stride=2, padding=1), 0.2) for a 4x4 weight (FCDiscriminator's layers)"""
-    return _DiscConvFn.apply(x, weight, bias, bool(leaky))
+def disc_conv4x4s2(x, weight, bias, leaky, fmt=None):
+    """leaky_relu?(F.conv2d(x, weight, bias, stride=2, padding=1), 0.2) for a 4x4 weight (FCDiscriminator's layers).
+    fmt = None: fp32 arithmetic; torch.float16 / torch.bfloat16: operands rounded to that type on the matrix cores, fp32
+    accumulation (what autocast's convolution computes), with fp32 tensors in and out either way"""
+    if fmt is None:
+        return _DiscConvFn.apply(x, weight, bias, bool(leaky))
+    if fmt not in (torch.float16, torch.bfloat16):
+        raise TypeError("fmt must be None, torch.float16 or torch.bfloat16, got %r" % (fmt,))
+    return _DiscConvFn.apply(x, weight, bias, bool(leaky), fmt)
 
 
 def _sync_world(bn):

@@ -1701,8 +1701,18 @@ def _disc_conv_shapes(x, weight):
     return B, Cin, Cout, H, W, (H - 2) // 2 + 1, (W - 2) // 2 + 1
 
 
-def disc_conv_fwd(x, weight, bias, leaky):
-    """x [B,Cin,H,W], weight [Cout,Cin,4,4], bias [Cout] or None, fp32 NCHW -> leaky_relu?(conv2d(x, w, b, stride 2, padding 1))"""
+def _disc_fmt(fmt):
+    """FMT_FP16 / FMT_BF16 or torch.float16 / torch.bfloat16 -> the HIAST_FMT_* code of the matrix-core entries"""
+    if isinstance(fmt, torch.dtype):
+        if fmt not in _H16:
+            raise TypeError("the 16-bit discriminator convolutions take float16 or bfloat16, got %s" % fmt)
+        return FMT_FP16 if fmt == torch.float16 else FMT_BF16
+    if fmt is None or int(fmt) not in (FMT_FP16, FMT_BF16):
+        raise ValueError("fmt must be FMT_FP16 or FMT_BF16, got %r" % (fmt,))
+    return int(fmt)
+
+
+def _disc_conv_fwd(x, weight, bias, leaky, fmt):
     _req(x, torch.float32, 4, "x")
     _req(weight, torch.float32, 4, "weight")
     B, Cin, Cout, H, W, Ho, Wo = _disc_conv_shapes(x, weight)
@@ -1710,13 +1720,16 @@ def disc_conv_fwd(x, weight, bias, leaky):
         _req(bias, torch.float32, 1, "bias")
         assert bias.numel() == Cout
     y = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    check(_lib.load().hiast_disc_conv_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), B, Cin, Cout, H, W, int(bool(leaky)),
-                                          _stream()), "hiast_disc_conv_fwd")
+    lib = _lib.load()
+    args = (_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), B, Cin, Cout, H, W, int(bool(leaky)))
+    if fmt is None:
+        check(lib.hiast_disc_conv_fwd(*args, _stream()), "hiast_disc_conv_fwd")
+    else:
+        check(lib.hiast_disc_conv16_fwd(*args, fmt, _stream()), "hiast_disc_conv16_fwd")
     return y
 
 
-def disc_conv_dgrad(dy, y, weight, x_shape, leaky):
-    """dy, y [B,Cout,Ho,Wo] (y = the layer's saved output: the LeakyReLU gate), weight [Cout,Cin,4,4] -> dx [B,Cin,H,W]"""
+def _disc_conv_dgrad(dy, y, weight, x_shape, leaky, fmt):
     _req(dy, torch.float32, 4, "dy")
     _req(weight, torch.float32, 4, "weight")
     x_shape = tuple(int(s) for s in x_shape)
@@ -1727,13 +1740,17 @@ def disc_conv_dgrad(dy, y, weight, x_shape, leaky):
         assert y.shape == dy.shape
     ws = _disc_conv_ws(x_shape, Cout, dy.device)
     dx = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
-    check(_lib.load().hiast_disc_conv_dgrad(_ptr(dy), _ptr(y if leaky else None), _ptr(weight), _ptr(dx), B, Cin, Cout, H, W,
-                                            int(bool(leaky)), _ptr(ws), ws.numel() * 4, _stream()), "hiast_disc_conv_dgrad")
+    lib = _lib.load()
+    args = (_ptr(dy), _ptr(y if leaky else None), _ptr(weight), _ptr(dx), B, Cin, Cout, H, W, int(bool(leaky)))
+    tail = (_ptr(ws), ws.numel() * 4, _stream())
+    if fmt is None:
+        check(lib.hiast_disc_conv_dgrad(*args, *tail), "hiast_disc_conv_dgrad")
+    else:
+        check(lib.hiast_disc_conv16_dgrad(*args, fmt, *tail), "hiast_disc_conv16_dgrad")
     return dx
 
 
-def disc_conv_wgrad(x, dy, y, leaky, want_bias=True):
-    """x [B,Cin,H,W], dy, y [B,Cout,Ho,Wo] -> (dW [Cout,Cin,4,4], db [Cout] or None); bit-reproducible (fixed-order second stage)"""
+def _disc_conv_wgrad(x, dy, y, leaky, want_bias, fmt):
     _req(x, torch.float32, 4, "x")
     _req(dy, torch.float32, 4, "dy")
     B, Cin, H, W = x.shape
@@ -1745,6 +1762,40 @@ def disc_conv_wgrad(x, dy, y, leaky, want_bias=True):
     ws = _disc_conv_ws(tuple(x.shape), Cout, x.device)
     dw = torch.empty((Cout, Cin, 4, 4), dtype=torch.float32, device=x.device)
     db = torch.empty((Cout,), dtype=torch.float32, device=x.device) if want_bias else None
-    check(_lib.load().hiast_disc_conv_wgrad(_ptr(x), _ptr(dy), _ptr(y if leaky else None), _ptr(dw), _ptr(db), B, Cin, Cout, H, W,
-                                            int(bool(leaky)), _ptr(ws), ws.numel() * 4, _stream()), "hiast_disc_conv_wgrad")
+    lib = _lib.load()
+    args = (_ptr(x), _ptr(dy), _ptr(y if leaky else None), _ptr(dw), _ptr(db), B, Cin, Cout, H, W, int(bool(leaky)))
+    tail = (_ptr(ws), ws.numel() * 4, _stream())
+    if fmt is None:
+        check(lib.hiast_disc_conv_wgrad(*args, *tail), "hiast_disc_conv_wgrad")
+    else:
+        check(lib.hiast_disc_conv16_wgrad(*args, fmt, *tail), "hiast_disc_conv16_wgrad")
     return dw, db
+
+
+def disc_conv_fwd(x, weight, bias, leaky):
+    """x [B,Cin,H,W], weight [Cout,Cin,4,4], bias [Cout] or None, fp32 NCHW -> leaky_relu?(conv2d(x, w, b, stride 2, padding 1))"""
+    return _disc_conv_fwd(x, weight, bias, leaky, None)
+
+
+def disc_conv_dgrad(dy, y, weight, x_shape, leaky):
+    """dy, y [B,Cout,Ho,Wo] (y = the layer's saved output: the LeakyReLU gate), weight [Cout,Cin,4,4] -> dx [B,Cin,H,W]"""
+    return _disc_conv_dgrad(dy, y, weight, x_shape, leaky, None)
+
+
+def disc_conv_wgrad(x, dy, y, leaky, want_bias=True):
+    """x [B,Cin,H,W], dy, y [B,Cout,Ho,Wo] -> (dW [Cout,Cin,4,4], db [Cout] or None); bit-reproducible (fixed-order second stage)"""
+    return _disc_conv_wgrad(x, dy, y, leaky, want_bias, None)
+
+
+# the same three on the matrix cores (hiast_disc_conv16_*): fp32 tensors in and out, operands rounded to fmt (FMT_FP16 | FMT_BF16
+# or torch.float16 | torch.bfloat16) as they are staged, fp32 accumulation
+def disc_conv16_fwd(x, weight, bias, leaky, fmt):
+    return _disc_conv_fwd(x, weight, bias, leaky, _disc_fmt(fmt))
+
+
+def disc_conv16_dgrad(dy, y, weight, x_shape, leaky, fmt):
+    return _disc_conv_dgrad(dy, y, weight, x_shape, leaky, _disc_fmt(fmt))
+
+
+def disc_conv16_wgrad(x, dy, y, leaky, fmt, want_bias=True):
+    return _disc_conv_wgrad(x, dy, y, leaky, want_bias, _disc_fmt(fmt))

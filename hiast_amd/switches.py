@@ -9,7 +9,7 @@ _NAMES = ("HIAST_NO_BN_MASK", "HIAST_NO_BN_BWD_FUSION", "HIAST_LIB_WGRAD", "HIAS
           "HIAST_NO_IDT_HANDOFF", "HIAST_LIB_STEM")
 SWITCHES = {n: os.environ.get(n, "0") == "1" for n in _NAMES}
 # opt-IN paths (off unless set to "1"), kept apart from the opt-outs above; read once and flipped by tests the same way
-_OPT_IN_NAMES = ("HIAST_DISC_HIP",)
+_OPT_IN_NAMES = ("HIAST_DISC_HIP", "HIAST_DISC_HIP_16BIT")
 OPT_IN = {n: os.environ.get(n, "0") == "1" for n in _OPT_IN_NAMES}
 
 

@@ -634,6 +634,17 @@ int hiast_disc_conv_dgrad(const float* dy, const float* y, const float* w, float
                           int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
 int hiast_disc_conv_wgrad(const float* x, const float* dy, const float* y, float* dw, float* db, int B, int Cin, int Cout,
                           int H, int W, int leaky, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
+/* The same three operations on the matrix cores: same tensors (fp32 NCHW in memory), same workspace, same checks and return
+ * codes; fmt = HIAST_FMT_FP16 | HIAST_FMT_BF16 (anything else: HIAST_E_ARG, nothing launched).  Every operand value (x, w;
+ * in the backward the fp32 product dy * slope, w and x) is rounded to fmt, nearest even, as it is staged — an fp16 overflow is
+ * +-inf, not a clamp — and the products are summed in fp32.  Outputs are fp32.  wgrad keeps the split and the fixed-order
+ * second stage of the fp32 entry: bit-reproducible. */
+int hiast_disc_conv16_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int H, int W,
+                          int leaky, int fmt, hiast_stream_t stream);
+int hiast_disc_conv16_dgrad(const float* dy, const float* y, const float* w, float* dx, int B, int Cin, int Cout, int H, int W,
+                            int leaky, int fmt, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
+int hiast_disc_conv16_wgrad(const float* x, const float* dy, const float* y, float* dw, float* db, int B, int Cin, int Cout,
+                            int H, int W, int leaky, int fmt, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
 
 /* ---- K12: IoU histograms --------------------------------------------------------------
  * utils/metrics.py:6-19 intersectionAndUnionGPU: pred/target int64 [N]; target==255 is
