@@ -10,6 +10,8 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/hiast_hip.h"
 
 #define HIAST_WAVE 64
@@ -32,6 +34,20 @@ int hiast_cu_count();
 int hiast_grid_cus();
 
 namespace hiast {
+
+// The class counts that the kernels with one register per class (st_loss, dinput) are instantiated for (host):
+// calls f(std::integral_constant<int, C>{}); false, and no call, for any other C.
+template <class F>
+static inline bool for_class_count(int C, F&& f)
+{
+    switch (C) {
+        case 19: f(std::integral_constant<int, 19>{}); return true;
+        case 16: f(std::integral_constant<int, 16>{}); return true;
+        case 9:  f(std::integral_constant<int, 9>{});  return true;
+        case 2:  f(std::integral_constant<int, 2>{});  return true;
+        default: return false;
+    }
+}
 
 // ---- the two 16-bit storage types of the mixed-precision path (operand format HIAST_FMT_BF16 / HIAST_FMT_FP16) ----------
 // The reference trains under apex O1 = IEEE fp16 (code/utils/default_config.py:109, utils/utils.py:126-132); bf16 is

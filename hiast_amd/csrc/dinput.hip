@@ -101,15 +101,6 @@ static int dinput_check(const void* a, const void* b, int mode, int B, int C, in
     return 0;
 }
 
-#define HIAST_DIN_DISPATCH(KERNEL_CALL)                                           \
-    switch (C) {                                                                  \
-        case 19: { constexpr int CC = 19; KERNEL_CALL; } break;                   \
-        case 16: { constexpr int CC = 16; KERNEL_CALL; } break;                   \
-        case 9:  { constexpr int CC = 9;  KERNEL_CALL; } break;                   \
-        case 2:  { constexpr int CC = 2;  KERNEL_CALL; } break;                   \
-        default: return HIAST_E_RANGE;                                            \
-    }
-
 extern "C" int hiast_dinput_fwd(const float* logits_lr, int mode, float* out, int B, int C, int h, int w, int H,
                                 int W, hiast_stream_t stream)
 {
@@ -118,10 +109,14 @@ extern "C" int hiast_dinput_fwd(const float* logits_lr, int mode, float* out, in
     const float sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.0f;
     const float sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.0f;
     dim3 grid((W + 255) / 256, H, B);
-#define FWD(M) hipLaunchKernelGGL((hiast::dinput_fwd_kernel<CC, M>), grid, dim3(256), 0, (hipStream_t)stream, \
-                                  logits_lr, out, h, w, H, W, sh, sw)
-    if (mode == 0) { HIAST_DIN_DISPATCH(FWD(0)) } else { HIAST_DIN_DISPATCH(FWD(1)) }
-#undef FWD
+    auto launch = [&](auto cc, auto mm) {
+        hipLaunchKernelGGL((hiast::dinput_fwd_kernel<decltype(cc)::value, decltype(mm)::value>), grid, dim3(256), 0,
+                           (hipStream_t)stream, logits_lr, out, h, w, H, W, sh, sw);
+    };
+    const bool known = hiast::for_class_count(C, [&](auto cc) {
+        if (mode == 0) launch(cc, std::integral_constant<int, 0>{}); else launch(cc, std::integral_constant<int, 1>{});
+    });
+    if (!known) return HIAST_E_RANGE;
     HIAST_CHECK_LAUNCH();
     return 0;
 }
@@ -135,10 +130,14 @@ extern "C" int hiast_dinput_bwd(const float* logits_lr, int mode, const float* g
     const float sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.0f;
     const float sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.0f;
     dim3 grid((W + 255) / 256, H, B);
-#define BWD(M) hipLaunchKernelGGL((hiast::dinput_bwd_kernel<CC, M>), grid, dim3(256), 0, (hipStream_t)stream, \
-                                  logits_lr, gout, scratch, h, w, H, W, sh, sw)
-    if (mode == 0) { HIAST_DIN_DISPATCH(BWD(0)) } else { HIAST_DIN_DISPATCH(BWD(1)) }
-#undef BWD
+    auto launch = [&](auto cc, auto mm) {
+        hipLaunchKernelGGL((hiast::dinput_bwd_kernel<decltype(cc)::value, decltype(mm)::value>), grid, dim3(256), 0,
+                           (hipStream_t)stream, logits_lr, gout, scratch, h, w, H, W, sh, sw);
+    };
+    const bool known = hiast::for_class_count(C, [&](auto cc) {
+        if (mode == 0) launch(cc, std::integral_constant<int, 0>{}); else launch(cc, std::integral_constant<int, 1>{});
+    });
+    if (!known) return HIAST_E_RANGE;
     HIAST_CHECK_LAUNCH();
     return hiast_upsample_bilinear_ac_bwd(scratch, dlogits_lr, B, C, h, w, H, W, stream);
 }

@@ -23,8 +23,18 @@
 //   2 KLDIV   q_c (log q_c - logp_c)                q = softmax(q1): LOSS['KLDIV'] applies a softmax to the probabilities
 //                                                   it is handed (losses.py:21-23) — a double softmax, kept
 //   3 MSE     (z_c - q1_c)^2                        on the raw student logits (losses.py:9-13)
-// KIND 0 compiles to the instructions it had before the other kinds existed (its code sits in `if constexpr (KIND == 0)`
-// blocks of its own, untouched).
+//
+// Each step is written once, as a helper: the band prologue (load_band), the teacher's max / 1/Σexp / arg-max (soft_stats),
+// q1_c (teacher_prob), KLDIV's Σ exp(q1) (teacher_exp_sum), the entropy of the ignored pixels (entropy).  A pixel is then:
+// the student part common to all kinds, the entropy, one consistency block per kind.  The library is built with
+// -ffp-contract=off -fno-fast-math, so a helper computes the bits of the expression spelled out.  Where a helper changed the
+// registers or the instruction count of a kernel against the spelled-out form, the spelled-out form stays:
+//   fwd SoftCE keeps the entropy and its element in ONE loop over c: with entropy() ahead of the element loop its kernels
+//     need 70 -> 79 VGPRs at C = 9 (7 -> 6 waves per SIMD) and 133 -> 136 at C = 16, with it behind 146 -> 151 at C = 19 too;
+//   bwd spells its own prologue and its own teacher max / Σexp loop: with soft_stats (returning a struct or writing through
+//     references alike) 16 of its kernels change their register counts (C = 19: 200 / 201 / 189 -> 184 / 184 / 187) and run
+//     0.4 - 1.5 % SLOWER, and with load_band 10 change their instruction counts; entropy, teacher_prob and teacher_exp_sum
+//     leave all 40 bwd kernels with the registers and the instructions they had.
 #include "common.h"
 
 namespace hiast {
@@ -49,6 +59,75 @@ __device__ __forceinline__ int region_count(const LT* plbl, int B, int H, int W,
     return M;
 }
 
+// band prologue: the horizontally-lerped values of the C classes of image b on the band's two source rows y0 / y1
+template <int C>
+__device__ __forceinline__ void load_band(const float* __restrict__ lr, int b, int h, int w, int y0, int y1,
+                                          const Src& sx, float (&top)[C], float (&bot)[C])
+{
+    const float* base = lr + (size_t)b * C * h * w;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float* p = base + (size_t)c * h * w;
+        top[c] = lerp_h(p[y0 * w + sx.i0], p[y0 * w + sx.i1], sx.l0, sx.l1);
+        bot[c] = lerp_h(p[y1 * w + sx.i0], p[y1 * w + sx.i1], sx.l0, sx.l1);
+    }
+}
+
+// softmax statistics of the C vertically-lerped values of one pixel: maximum, 1 / Σ exp(. - maximum) and the index of the
+// first maximum (torch.argmax / torch.max: the first one wins).  What a caller does not use is dropped by the compiler.
+struct SoftStats {
+    float m, invS;
+    int arg;
+};
+
+template <int C>
+__device__ __forceinline__ SoftStats soft_stats(const float (&top)[C], const float (&bot)[C], const Src& sy)
+{
+    SoftStats r = {0.f, 0.f, 0};
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float z = lerp_v(top[c], bot[c], sy.l0, sy.l1);
+        const bool up = (c == 0 || z > r.m);
+        r.m = up ? z : r.m;
+        r.arg = up ? c : r.arg;
+    }
+    float S = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) S += __expf(lerp_v(top[c], bot[c], sy.l0, sy.l1) - r.m);
+    r.invS = 1.0f / S;
+    return r;
+}
+
+// q1_c = softmax(zt)_c of the teacher, in fp32
+__device__ __forceinline__ float teacher_prob(float top, float bot, const Src& sy, float mt, float invSt)
+{
+    return __expf(lerp_v(top, bot, sy.l0, sy.l1) - mt) * invSt;
+}
+
+// KLDIV: S2 = Σ exp(q1_c), the denominator of q = softmax(q1); q1 in [0, 1], exp(q1) in [1, e]: no shift needed
+template <int C>
+__device__ __forceinline__ float teacher_exp_sum(const float (&tt)[C], const float (&tb)[C], const Src& sy,
+                                                 float mt, float invSt)
+{
+    float S2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) S2 += __expf(teacher_prob(tt[c], tb[c], sy, mt, invSt));
+    return S2;
+}
+
+// -Σ p_c log p_c of the student, lse = log Σ exp z
+template <int C>
+__device__ __forceinline__ float entropy(const float (&st)[C], const float (&sb)[C], const Src& sy, float lse)
+{
+    float e = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
+        e -= __expf(logp) * logp;
+    }
+    return e;
+}
+
 // ------------------------------------------------------------------------------------------ fwd
 template <int C, bool TEACHER, typename LT, int KIND = CST_SOFTCE>
 __global__ __launch_bounds__(LOSS_THREADS) void st_loss_fwd_kernel(
@@ -63,25 +142,10 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_fwd_kernel(
     const Src sx = src_of(sw, Xc, w);
     const int y0 = j, y1 = j + (j < h - 1 ? 1 : 0);
 
+    static_assert(TEACHER || KIND == CST_SOFTCE, "the CE / KLDIV / MSE consistency kinds need the teacher");
     float st[C], sb[C], tt[TEACHER ? C : 1], tb[TEACHER ? C : 1];
-    {
-        const float* base = zs_lr + (size_t)b * C * h * w;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float* p = base + (size_t)c * h * w;
-            st[c] = lerp_h(p[y0 * w + sx.i0], p[y0 * w + sx.i1], sx.l0, sx.l1);
-            sb[c] = lerp_h(p[y1 * w + sx.i0], p[y1 * w + sx.i1], sx.l0, sx.l1);
-        }
-        if (TEACHER) {
-            const float* tbase = zt_lr + (size_t)b * C * h * w;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float* p = tbase + (size_t)c * h * w;
-                tt[c] = lerp_h(p[y0 * w + sx.i0], p[y0 * w + sx.i1], sx.l0, sx.l1);
-                tb[c] = lerp_h(p[y1 * w + sx.i0], p[y1 * w + sx.i1], sx.l0, sx.l1);
-            }
-        }
-    }
+    load_band<C>(zs_lr, b, h, w, y0, y1, sx, st, sb);
+    if constexpr (TEACHER) load_band<C>(zt_lr, b, h, w, y0, y1, sx, tt, tb);
 
     float a_ce = 0.f, a_kld = 0.f, a_ent = 0.f, a_cst = 0.f;
     int n_conf = 0, n_ign = 0, n_cst = 0;
@@ -91,6 +155,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_fwd_kernel(
             const Src sy = src_of(sh, Y, h);
             const int y = load_label(plbl, ((size_t)b * H + Y) * W + X);
             const bool ign = (y == HIAST_IGNORE);
+            // student: CE on the pseudo-label and KLD to uniform where it is confident, entropy where it is ignored
             float ms = 0.f, zy = 0.f, zsum = 0.f;
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -108,21 +173,15 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_fwd_kernel(
                 a_kld += ((float)C * lse - zsum) * invC;
                 ++n_conf;
             } else {
+                if constexpr (KIND != CST_SOFTCE) a_ent += entropy(st, sb, sy, lse);
                 ++n_ign;
             }
+            // consistency with the teacher: slot 3 the sum of the elements, slot 6 the count of the non-zero ones (losses.py:89)
             const bool in_region = TEACHER && (region == 2 || (region == 0 ? ign : !ign));
-            if constexpr (KIND == CST_SOFTCE) {
-                float mt = 0.f, invSt = 0.f;
-                if (TEACHER && in_region) {
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
-                        mt = (c == 0 || z > mt) ? z : mt;
-                    }
-                    float St = 0.f;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) St += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt);
-                    invSt = 1.0f / St;
+            if constexpr (KIND == CST_SOFTCE) {            // one loop for the entropy and the element: see the header
+                SoftStats t = {0.f, 0.f, 0};
+                if constexpr (TEACHER) {
+                    if (in_region) t = soft_stats(tt, tb, sy);
                 }
                 if (ign || in_region) {
                     float e = 0.f, cs = 0.f;
@@ -131,90 +190,54 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_fwd_kernel(
                     for (int c = 0; c < C; ++c) {
                         const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
                         if (ign) e -= __expf(logp) * logp;
-                        if (TEACHER && in_region) {
-                            const float q = __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
-                            const float prod = (-logp) * q;        // losses.py:61
-                            cs += prod;
-                            cn += (prod != 0.0f) ? 1 : 0;          // losses.py:89
+                        if constexpr (TEACHER) {
+                            if (in_region) {
+                                const float prod = (-logp) * teacher_prob(tt[c], tb[c], sy, t.m, t.invS);    // losses.py:61
+                                cs += prod;
+                                cn += (prod != 0.0f) ? 1 : 0;
+                            }
                         }
                     }
                     a_ent += e;
                     a_cst += cs;
                     n_cst += cn;
                 }
-            } else {
-                static_assert(TEACHER, "the CE / KLDIV / MSE consistency kinds need the teacher");
-                if (ign) {
-                    float e = 0.f;
+            } else if constexpr (KIND == CST_CE) {
+                const int M = region_count(plbl, (int)gridDim.z, H, W, Y, X, region);
+                if (M > 0) {
+                    const int yt = soft_stats(tt, tb, sy).arg;
+                    float zyt = 0.f;
 #pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
-                        e -= __expf(logp) * logp;
-                    }
-                    a_ent += e;
+                    for (int c = 0; c < C; ++c) zyt = (c == yt) ? lerp_v(st[c], sb[c], sy.l0, sy.l1) : zyt;
+                    const float l = lse - zyt;             // losses.py:35, reduction='none'
+                    a_cst += l * (float)M;                 // Σ_i l[j] mask[i], losses.py:86-87
+                    n_cst += (l != 0.0f) ? M : 0;
                 }
-                if constexpr (KIND == CST_CE) {
-                    const int M = region_count(plbl, (int)gridDim.z, H, W, Y, X, region);
-                    if (M > 0) {
-                        float mt = 0.f;
-                        int yt = 0;
+            } else if (in_region) {                        // KLDIV, MSE
+                const SoftStats t = soft_stats(tt, tb, sy);
+                float invS2 = 0.f, logS2 = 0.f;                        // KLDIV: q = softmax(q1) = exp(q1 - logS2)
+                if constexpr (KIND == CST_KLDIV) {
+                    const float S2 = teacher_exp_sum(tt, tb, sy, t.m, t.invS);
+                    invS2 = 1.0f / S2;
+                    logS2 = __logf(S2);
+                }
+                float cs = 0.f;
+                int cn = 0;
 #pragma unroll
-                        for (int c = 0; c < C; ++c) {          // first maximum wins (torch.argmax / torch.max)
-                            const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
-                            const bool up = (c == 0 || z > mt);
-                            mt = up ? z : mt;
-                            yt = up ? c : yt;
-                        }
-                        float zyt = 0.f;
-#pragma unroll
-                        for (int c = 0; c < C; ++c) zyt = (c == yt) ? lerp_v(st[c], sb[c], sy.l0, sy.l1) : zyt;
-                        const float l = lse - zyt;             // losses.py:35, reduction='none'
-                        a_cst += l * (float)M;                 // Σ_i l[j] mask[i], losses.py:86-87
-                        n_cst += (l != 0.0f) ? M : 0;          // losses.py:89
-                    }
-                } else if (in_region) {
-                    float mt = 0.f;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float z = lerp_v(tt[c], tb[c], sy.l0, sy.l1);
-                        mt = (c == 0 || z > mt) ? z : mt;
-                    }
-                    float St = 0.f;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) St += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt);
-                    const float invSt = 1.0f / St;
-                    float cs = 0.f;
-                    int cn = 0;
+                for (int c = 0; c < C; ++c) {
+                    const float z = lerp_v(st[c], sb[c], sy.l0, sy.l1);
+                    const float q1 = teacher_prob(tt[c], tb[c], sy, t.m, t.invS);
+                    float prod;
                     if constexpr (KIND == CST_KLDIV) {
-                        // q = softmax(q1), q1 in [0, 1]: exp(q1) in [1, e], no shift needed
-                        float S2 = 0.f;
-#pragma unroll
-                        for (int c = 0; c < C; ++c)
-                            S2 += __expf(__expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt);
-                        const float invS2 = 1.0f / S2, logS2 = __logf(S2);
-#pragma unroll
-                        for (int c = 0; c < C; ++c) {
-                            const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
-                            const float q1 = __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
-                            const float q = __expf(q1) * invS2;
-                            const float prod = q * ((q1 - logS2) - logp);   // nn.KLDivLoss: q (log q - logp)
-                            cs += prod;
-                            cn += (prod != 0.0f) ? 1 : 0;
-                        }
+                        prod = (__expf(q1) * invS2) * ((q1 - logS2) - (z - lse));        // nn.KLDivLoss: q (log q - logp)
                     } else {
-#pragma unroll
-                        for (int c = 0; c < C; ++c) {
-                            const float z = lerp_v(st[c], sb[c], sy.l0, sy.l1);
-                            const float q1 = __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
-                            const float d = z - q1;
-                            const float prod = d * d;                       // nn.MSELoss on the raw logits
-                            cs += prod;
-                            cn += (prod != 0.0f) ? 1 : 0;
-                        }
+                        prod = (z - q1) * (z - q1);                                      // nn.MSELoss on the raw logits
                     }
-                    a_cst += cs;
-                    n_cst += cn;
+                    cs += prod;
+                    cn += (prod != 0.0f) ? 1 : 0;
                 }
+                a_cst += cs;
+                n_cst += cn;
             }
         }
     }
@@ -286,6 +309,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
     const float A3 = c2 == 0.f ? 0.f : (float)((double)c2 / ((double)C * sums[5]));
     const float A4 = (!TEACHER || c3 == 0.f) ? 0.f : (float)((double)c3 / sums[6]);
 
+    static_assert(TEACHER || KIND == CST_SOFTCE, "the CE / KLDIV / MSE consistency kinds need the teacher");
     float st[C], sb[C], tt[TEACHER ? C : 1], tb[TEACHER ? C : 1];
     float gt[C], gb[C];
 #pragma unroll
@@ -327,14 +351,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
 #pragma unroll
             for (int c = 0; c < C; ++c) Ss += __expf(lerp_v(st[c], sb[c], sy.l0, sy.l1) - ms);
             const float lse = ms + __logf(Ss);
-            float Hent = 0.f;
-            if (ign) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float logp = lerp_v(st[c], sb[c], sy.l0, sy.l1) - lse;
-                    Hent -= __expf(logp) * logp;
-                }
-            }
+            const float Hent = ign ? entropy(st, sb, sy, lse) : 0.f;
             float mt = 0.f, invSt = 0.f, Q = 0.f;
             // KIND 1 (CE): every pixel with M > 0 carries the term, yt = arg-max of the teacher; KIND 2: invS2 / Q of q = softmax(q1)
             int yt = 0;
@@ -353,16 +370,13 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
                 invSt = 1.0f / St;
                 if constexpr (KIND == CST_SOFTCE) {
 #pragma unroll
-                    for (int c = 0; c < C; ++c) Q += __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt;
+                    for (int c = 0; c < C; ++c) Q += teacher_prob(tt[c], tb[c], sy, mt, invSt);
                 }
                 if constexpr (KIND == CST_KLDIV) {
-                    float S2 = 0.f;
-#pragma unroll
-                    for (int c = 0; c < C; ++c) S2 += __expf(__expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt);
-                    invS2 = 1.0f / S2;
+                    invS2 = 1.0f / teacher_exp_sum(tt, tb, sy, mt, invSt);
 #pragma unroll
                     for (int c = 0; c < C; ++c)
-                        Q += __expf(__expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt) * invS2;
+                        Q += __expf(teacher_prob(tt[c], tb[c], sy, mt, invSt)) * invS2;
                 }
             }
 #pragma unroll
@@ -375,7 +389,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
                 if constexpr (KIND == CST_SOFTCE) {
                     if (TEACHER) {
                         const float q = in_region
-                                            ? __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt
+                                            ? teacher_prob(tt[c], tb[c], sy, mt, invSt)
                                             : 0.f;
                         g += A4 * (wreg * (p * Q - q));                              // soft CE
                     }
@@ -383,7 +397,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void st_loss_bwd_kernel(
                     g += A4 * (wM * (p - (c == yt ? 1.f : 0.f)));                    // CE on the teacher's arg-max, M-fold
                 } else {
                     const float q1 = in_region
-                                         ? __expf(lerp_v(tt[c], tb[c], sy.l0, sy.l1) - mt) * invSt
+                                         ? teacher_prob(tt[c], tb[c], sy, mt, invSt)
                                          : 0.f;
                     if constexpr (KIND == CST_KLDIV) {
                         const float q = in_region ? __expf(q1) * invS2 : 0.f;
@@ -492,115 +506,103 @@ extern "C" size_t hiast_st_loss_workspace_bytes(int B, int C, int h, int w, int 
     return (fwd > bwd ? fwd : bwd) + 256;
 }
 
-static int loss_check(const void* a, const void* l, const void* s, const void* ws, int B, int C, int h,
-                      int w, int H, int W, int region)
+// The argument checks of both entries, in the order in which they report; fills the geometry.  `outs`: false when one of the
+// pointers that only bwd takes is NULL.  cst_kind: 0..3 (HIAST_CST_*); kinds other than SoftCE need the teacher.
+static int loss_check(const float* logits_lr, const float* teacher_lr, const void* plbl, int B, int C, int h, int w,
+                      int H, int W, int region, int cst_kind, const double* sums, bool outs, const void* workspace,
+                      size_t workspace_bytes, hiast::LossGeom* g)
 {
-    if (!a || !l || !s || !ws) return HIAST_E_ARG;
+    if (!logits_lr || !plbl || !sums || !workspace) return HIAST_E_ARG;
     if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return HIAST_E_ARG;
     if (H < h || W < w || B > 65535 || h > 65535 || region < 0 || region > 2) return HIAST_E_RANGE;
-    return 0;
-}
-
-#define HIAST_LOSS_DISPATCH(KERNEL_CALL)                                          \
-    switch (C) {                                                                  \
-        case 19: { constexpr int CC = 19; KERNEL_CALL; } break;                   \
-        case 16: { constexpr int CC = 16; KERNEL_CALL; } break;                   \
-        case 9:  { constexpr int CC = 9;  KERNEL_CALL; } break;                   \
-        case 2:  { constexpr int CC = 2;  KERNEL_CALL; } break;                   \
-        default: return HIAST_E_RANGE;                                            \
-    }
-
-// cst_kind: 0..3 (HIAST_CST_*); kinds other than SoftCE need the teacher
-static int loss_kind_check(int cst_kind, const float* teacher_lr)
-{
+    if (!outs) return HIAST_E_ARG;
     if (cst_kind < 0 || cst_kind > 3) return HIAST_E_RANGE;
     if (cst_kind != 0 && !teacher_lr) return HIAST_E_ARG;
+    if (const int e = hiast::loss_geom(h, w, H, W, g)) return e;
+    if (workspace_bytes < hiast_st_loss_workspace_bytes(B, C, h, w, H, W)) return HIAST_E_WS;
     return 0;
 }
 
-#define HIAST_LOSS_KINDS(CALL)                                                                     \
-    switch (cst_kind) {                                                                            \
-        case 1: { HIAST_LOSS_DISPATCH(CALL(hiast::CST_CE)) } break;                                \
-        case 2: { HIAST_LOSS_DISPATCH(CALL(hiast::CST_KLDIV)) } break;                             \
-        default: { HIAST_LOSS_DISPATCH(CALL(hiast::CST_MSE)) } break;                              \
-    }
+// The template arguments of the two kernels as one tag, and the switch from the run-time arguments to it: f(LossCfg<...>{})
+// for one of the 4 class counts x (SoftCE without / with teacher, CE, KLDIV, MSE) x (u8, i64 labels) = 40 configurations;
+// false, and no call, for any other class count.  The kind has passed loss_check.
+template <int C_, bool TEACHER_, typename LT_, int KIND_>
+struct LossCfg {
+    static constexpr int C = C_, KIND = KIND_;
+    static constexpr bool TEACHER = TEACHER_;
+    using LT = LT_;
+};
 
-static int loss_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl, int plbl_is_i64, int B,
-                    int C, int h, int w, int H, int W, int region, int cst_kind, double* sums, void* workspace,
-                    size_t workspace_bytes, hiast_stream_t stream)
+template <int C, bool TEACHER, int KIND, class F>
+static void loss_dispatch_labels(bool i64, F& f)
 {
-    int e = loss_check(logits_lr, plbl, sums, workspace, B, C, h, w, H, W, region);
-    if (e) return e;
-    if ((e = loss_kind_check(cst_kind, teacher_lr))) return e;
+    if (i64) f(LossCfg<C, TEACHER, int64_t, KIND>{}); else f(LossCfg<C, TEACHER, uint8_t, KIND>{});
+}
+
+template <class F>
+static bool loss_dispatch(int C, bool teacher, bool i64, int cst_kind, F&& f)
+{
+    return hiast::for_class_count(C, [&](auto cc) {
+        constexpr int CC = decltype(cc)::value;
+        switch (cst_kind) {
+            case hiast::CST_SOFTCE:
+                if (teacher) loss_dispatch_labels<CC, true, hiast::CST_SOFTCE>(i64, f);
+                else loss_dispatch_labels<CC, false, hiast::CST_SOFTCE>(i64, f);
+                break;
+            case hiast::CST_CE: loss_dispatch_labels<CC, true, hiast::CST_CE>(i64, f); break;
+            case hiast::CST_KLDIV: loss_dispatch_labels<CC, true, hiast::CST_KLDIV>(i64, f); break;
+            default: loss_dispatch_labels<CC, true, hiast::CST_MSE>(i64, f); break;
+        }
+    });
+}
+
+extern "C" int hiast_st_loss_cst_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                                     int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
+                                     int cst_kind, double* sums, void* workspace, size_t workspace_bytes,
+                                     hiast_stream_t stream)
+{
     hiast::LossGeom g;
-    if ((e = hiast::loss_geom(h, w, H, W, &g))) return e;
-    if (workspace_bytes < hiast_st_loss_workspace_bytes(B, C, h, w, H, W)) return HIAST_E_WS;
+    const int e = loss_check(logits_lr, teacher_lr, plbl, B, C, h, w, H, W, region, cst_kind, sums,
+                             /* outs: fwd takes none */ true, workspace, workspace_bytes, &g);
+    if (e) return e;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((W + 255) / 256, h, B);
     const int nblk = (int)(grid.x * grid.y * grid.z);
     double* partial = (double*)workspace;
-#define FWD(T, LT)                                                                                  \
-    hipLaunchKernelGGL((hiast::st_loss_fwd_kernel<CC, T, LT>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
-                       logits_lr, teacher_lr, (const LT*)plbl, h, w, H, W, g.sh, g.sw, region, partial)
-#define FWD_K64(KD)                                                                                          \
-    hipLaunchKernelGGL((hiast::st_loss_fwd_kernel<CC, true, int64_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
-                       logits_lr, teacher_lr, (const int64_t*)plbl, h, w, H, W, g.sh, g.sw, region, partial)
-#define FWD_K8(KD)                                                                                           \
-    hipLaunchKernelGGL((hiast::st_loss_fwd_kernel<CC, true, uint8_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
-                       logits_lr, teacher_lr, (const uint8_t*)plbl, h, w, H, W, g.sh, g.sw, region, partial)
-    if (cst_kind != 0) {
-        if (plbl_is_i64) { HIAST_LOSS_KINDS(FWD_K64) } else { HIAST_LOSS_KINDS(FWD_K8) }
-    } else if (teacher_lr) {
-        if (plbl_is_i64) { HIAST_LOSS_DISPATCH(FWD(true, int64_t)) } else { HIAST_LOSS_DISPATCH(FWD(true, uint8_t)) }
-    } else {
-        if (plbl_is_i64) { HIAST_LOSS_DISPATCH(FWD(false, int64_t)) } else { HIAST_LOSS_DISPATCH(FWD(false, uint8_t)) }
-    }
-#undef FWD
-#undef FWD_K64
-#undef FWD_K8
+    const bool known = loss_dispatch(C, teacher_lr != nullptr, plbl_is_i64 != 0, cst_kind, [&](auto cfg) {
+        using Cfg = decltype(cfg);
+        using LT = typename Cfg::LT;
+        hipLaunchKernelGGL((hiast::st_loss_fwd_kernel<Cfg::C, Cfg::TEACHER, LT, Cfg::KIND>), grid,
+                           dim3(hiast::LOSS_THREADS), 0, st, logits_lr, teacher_lr, (const LT*)plbl, h, w, H, W, g.sh, g.sw,
+                           region, partial);
+    });
+    if (!known) return HIAST_E_RANGE;
     HIAST_CHECK_LAUNCH();
     hipLaunchKernelGGL(hiast::st_loss_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nblk, sums);
     HIAST_CHECK_LAUNCH();
     return 0;
 }
 
-static int loss_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl, int plbl_is_i64, int B,
-                    int C, int h, int w, int H, int W, int region, int cst_kind, const double* sums,
-                    const float* coef, float* dlogits_lr, void* workspace, size_t workspace_bytes,
-                    hiast_stream_t stream)
+extern "C" int hiast_st_loss_cst_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
+                                     int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
+                                     int cst_kind, const double* sums, const float* coef, float* dlogits_lr,
+                                     void* workspace, size_t workspace_bytes, hiast_stream_t stream)
 {
-    int e = loss_check(logits_lr, plbl, sums, workspace, B, C, h, w, H, W, region);
-    if (e) return e;
-    if (!coef || !dlogits_lr) return HIAST_E_ARG;
-    if ((e = loss_kind_check(cst_kind, teacher_lr))) return e;
     hiast::LossGeom g;
-    if ((e = hiast::loss_geom(h, w, H, W, &g))) return e;
-    if (workspace_bytes < hiast_st_loss_workspace_bytes(B, C, h, w, H, W)) return HIAST_E_WS;
+    const int e = loss_check(logits_lr, teacher_lr, plbl, B, C, h, w, H, W, region, cst_kind, sums, coef && dlogits_lr,
+                             workspace, workspace_bytes, &g);
+    if (e) return e;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(g.nxb, h, B);
     float* tiles = (float*)workspace;
-#define BWD(T, LT)                                                                                  \
-    hipLaunchKernelGGL((hiast::st_loss_bwd_kernel<CC, T, LT>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
-                       logits_lr, teacher_lr, (const LT*)plbl, h, w, H, W, g.sh, g.sw, region, g.TI,  \
-                       sums, coef, tiles)
-#define BWD_K64(KD)                                                                                          \
-    hipLaunchKernelGGL((hiast::st_loss_bwd_kernel<CC, true, int64_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
-                       logits_lr, teacher_lr, (const int64_t*)plbl, h, w, H, W, g.sh, g.sw, region, g.TI,     \
-                       sums, coef, tiles)
-#define BWD_K8(KD)                                                                                           \
-    hipLaunchKernelGGL((hiast::st_loss_bwd_kernel<CC, true, uint8_t, KD>), grid, dim3(hiast::LOSS_THREADS), 0, st, \
-                       logits_lr, teacher_lr, (const uint8_t*)plbl, h, w, H, W, g.sh, g.sw, region, g.TI,     \
-                       sums, coef, tiles)
-    if (cst_kind != 0) {
-        if (plbl_is_i64) { HIAST_LOSS_KINDS(BWD_K64) } else { HIAST_LOSS_KINDS(BWD_K8) }
-    } else if (teacher_lr) {
-        if (plbl_is_i64) { HIAST_LOSS_DISPATCH(BWD(true, int64_t)) } else { HIAST_LOSS_DISPATCH(BWD(true, uint8_t)) }
-    } else {
-        if (plbl_is_i64) { HIAST_LOSS_DISPATCH(BWD(false, int64_t)) } else { HIAST_LOSS_DISPATCH(BWD(false, uint8_t)) }
-    }
-#undef BWD
-#undef BWD_K64
-#undef BWD_K8
+    const bool known = loss_dispatch(C, teacher_lr != nullptr, plbl_is_i64 != 0, cst_kind, [&](auto cfg) {
+        using Cfg = decltype(cfg);
+        using LT = typename Cfg::LT;
+        hipLaunchKernelGGL((hiast::st_loss_bwd_kernel<Cfg::C, Cfg::TEACHER, LT, Cfg::KIND>), grid,
+                           dim3(hiast::LOSS_THREADS), 0, st, logits_lr, teacher_lr, (const LT*)plbl, h, w, H, W, g.sh, g.sw,
+                           region, g.TI, sums, coef, tiles);
+    });
+    if (!known) return HIAST_E_RANGE;
     HIAST_CHECK_LAUNCH();
     const long long total = (long long)B * C * h * w;
     hipLaunchKernelGGL(hiast::st_loss_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
@@ -609,22 +611,14 @@ static int loss_bwd(const float* logits_lr, const float* teacher_lr, const void*
     return 0;
 }
 
+// the entries from before the kinds existed: SoftCE
 extern "C" int hiast_st_loss_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
                                  int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
                                  double* sums, void* workspace, size_t workspace_bytes,
                                  hiast_stream_t stream)
 {
-    return loss_fwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, 0, sums, workspace,
-                    workspace_bytes, stream);
-}
-
-extern "C" int hiast_st_loss_cst_fwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
-                                     int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
-                                     int cst_kind, double* sums, void* workspace, size_t workspace_bytes,
-                                     hiast_stream_t stream)
-{
-    return loss_fwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, cst_kind, sums, workspace,
-                    workspace_bytes, stream);
+    return hiast_st_loss_cst_fwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, HIAST_CST_SOFTCE, sums,
+                                 workspace, workspace_bytes, stream);
 }
 
 extern "C" int hiast_st_loss_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
@@ -632,15 +626,6 @@ extern "C" int hiast_st_loss_bwd(const float* logits_lr, const float* teacher_lr
                                  const double* sums, const float* coef, float* dlogits_lr,
                                  void* workspace, size_t workspace_bytes, hiast_stream_t stream)
 {
-    return loss_bwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, 0, sums, coef, dlogits_lr,
-                    workspace, workspace_bytes, stream);
-}
-
-extern "C" int hiast_st_loss_cst_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
-                                     int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
-                                     int cst_kind, const double* sums, const float* coef, float* dlogits_lr,
-                                     void* workspace, size_t workspace_bytes, hiast_stream_t stream)
-{
-    return loss_bwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, cst_kind, sums, coef,
-                    dlogits_lr, workspace, workspace_bytes, stream);
+    return hiast_st_loss_cst_bwd(logits_lr, teacher_lr, plbl, plbl_is_i64, B, C, h, w, H, W, region, HIAST_CST_SOFTCE, sums,
+                                 coef, dlogits_lr, workspace, workspace_bytes, stream);
 }

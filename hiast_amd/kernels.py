@@ -327,42 +327,38 @@ def _cst_kind(cst_kind):
     return CST_KINDS[cst_kind] if isinstance(cst_kind, str) else int(cst_kind)
 
 
+def _loss_entry(name, kind, cst_entry):
+    """the C entry of one loss pass and its trailing `kind` argument: hiast_st_loss_<name>, or hiast_st_loss_cst_<name>
+    (which takes the kind) for any kind but 0 and where cst_entry asks for it"""
+    if kind != 0 or cst_entry:
+        return "hiast_st_loss_cst_" + name, (kind,)
+    return "hiast_st_loss_" + name, ()
+
+
 def st_loss_fwd(logits_lr, teacher_lr, plbl, H, W, region, workspace=None, cst_kind=0, cst_entry=False):
     """-> sums f64 [8] (device), see include/hiast_hip.h.  cst_kind: the consistency term (CST_KINDS name or number);
     0 goes through hiast_st_loss_fwd unless cst_entry asks for hiast_st_loss_cst_fwd."""
     B, C, h, w = _loss_args(logits_lr, teacher_lr, plbl, H, W)
-    kind = _cst_kind(cst_kind)
+    entry, kind = _loss_entry("fwd", _cst_kind(cst_kind), cst_entry)
     ws = workspace if workspace is not None else st_loss_workspace(B, C, h, w, H, W, logits_lr.device)
     sums = torch.empty(8, dtype=torch.float64, device=logits_lr.device)
-    if kind != 0 or cst_entry:
-        check(_lib.load().hiast_st_loss_cst_fwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
-                                                int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region], kind,
-                                                _ptr(sums), _ptr(ws), ws.numel() * 8, _stream()), "hiast_st_loss_cst_fwd")
-        return sums
-    check(_lib.load().hiast_st_loss_fwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
-                                        int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region],
-                                        _ptr(sums), _ptr(ws), ws.numel() * 8, _stream()), "hiast_st_loss_fwd")
+    check(getattr(_lib.load(), entry)(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl), int(plbl.dtype == torch.int64),
+                                      B, C, h, w, H, W, REGION[region], *kind,
+                                      _ptr(sums), _ptr(ws), ws.numel() * 8, _stream()), entry)
     return sums
 
 
 def st_loss_bwd(logits_lr, teacher_lr, plbl, H, W, region, sums, coef, workspace=None, cst_kind=0, cst_entry=False):
     B, C, h, w = _loss_args(logits_lr, teacher_lr, plbl, H, W)
-    kind = _cst_kind(cst_kind)
+    entry, kind = _loss_entry("bwd", _cst_kind(cst_kind), cst_entry)
     _req(sums, torch.float64, 1, "sums")
     _req(coef, torch.float32, 1, "coef")
     assert sums.numel() == 8 and coef.numel() == 4
     ws = workspace if workspace is not None else st_loss_workspace(B, C, h, w, H, W, logits_lr.device)
     d = torch.empty_like(logits_lr)
-    if kind != 0 or cst_entry:
-        check(_lib.load().hiast_st_loss_cst_bwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
-                                                int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region], kind,
-                                                _ptr(sums), _ptr(coef), _ptr(d), _ptr(ws), ws.numel() * 8, _stream()),
-              "hiast_st_loss_cst_bwd")
-        return d
-    check(_lib.load().hiast_st_loss_bwd(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl),
-                                        int(plbl.dtype == torch.int64), B, C, h, w, H, W, REGION[region],
-                                        _ptr(sums), _ptr(coef), _ptr(d), _ptr(ws), ws.numel() * 8, _stream()),
-          "hiast_st_loss_bwd")
+    check(getattr(_lib.load(), entry)(_ptr(logits_lr), _ptr(teacher_lr), _ptr(plbl), int(plbl.dtype == torch.int64),
+                                      B, C, h, w, H, W, REGION[region], *kind,
+                                      _ptr(sums), _ptr(coef), _ptr(d), _ptr(ws), ws.numel() * 8, _stream()), entry)
     return d
 
 
