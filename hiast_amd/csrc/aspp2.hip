@@ -19,13 +19,7 @@
 //                  transposing ds_read_b64_tr_b16; split over pixel ranges, fixed-order reduce)
 #include <hip/hip_bf16.h>
 
-#include "common.h"
-
-int hiast_gemm_nt_launch(const void* x, const float* w, void* y, int64_t M, int K, int N, int dtype, hipStream_t st);
-int hiast_igemm_launch(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                       const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N,
-                       int taps, int H, int W, int stride, int dil, int planes, int out_f32, hipStream_t st,
-                       float* stats, const void* res_gate, int gate_mask, int stats_rows);
+#include "conv_launch.h"
 
 namespace hiast {
 
@@ -405,9 +399,14 @@ extern "C" int hiast_aspp2_fwd(const void* x_nhwc, int dtype, const void* wt, co
     const bool t16 = dtype == HIAST_FMT_FP16 && !t32;
     if (dtype == 0)      // fp32 rows, fp32 weights: the register-staged kernel splits on the fly
         e = hiast_gemm_nt_launch(x_nhwc, (const float*)wt, T, M, Cin, NP, 0, st);
-    else                 // bf16 rows (1) / split planes (2) / fp16 rows (3), weights packed by hiast_pack_conv_weight: LDS-DMA kernel
-        e = hiast_igemm_launch(x_nhwc, wt, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, T, M, Cin, NP, 1, 0, 0,
-                               1, 1, dtype, t16 ? 0 : 1, st, nullptr, nullptr, 0, 0);
+    else {               // bf16 rows (1) / split planes (2) / fp16 rows (3), weights packed by hiast_pack_conv_weight: LDS-DMA kernel
+        ConvLaunch c;
+        c.x = x_nhwc; c.wp = wt; c.y = T;
+        c.M = M; c.K = Cin; c.N = NP;
+        c.fmt = dtype; c.out_f32 = t16 ? 0 : 1;
+        c.st = st;
+        e = hiast_igemm_launch(c);
+    }
     if (e) return e;
     const hiast::Taps2 taps = hiast::make_taps2(dil);
     const dim3 grid((h * w + 63) / 64, B);
@@ -450,8 +449,12 @@ extern "C" int hiast_aspp2_bwd(const void* x_nhwc, const float* dy, const void* 
     HIAST_CHECK_LAUNCH();
     if (dx_nhwc) {
         // dX[M][Cin] = G[M][NP] * wd[Cin][NP]^T, wd packed bf16 (hiast_pack_conv_weight, planes = 1)
-        e = hiast_igemm_launch(G, wd, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, 0, dx_nhwc, M, NP, Cin, 1, 0, 0, 1,
-                               1, fmt, 0, st, nullptr, nullptr, 0, 0);
+        ConvLaunch c;
+        c.x = G; c.wp = wd; c.y = dx_nhwc;
+        c.M = M; c.K = NP; c.N = Cin;
+        c.fmt = fmt;
+        c.st = st;
+        e = hiast_igemm_launch(c);
         if (e) return e;
     }
     if (want_w) {

@@ -60,6 +60,20 @@ typedef __attribute__((ext_vector_type(8))) _Float16 h_f16x8;
 typedef __attribute__((ext_vector_type(4))) float h_f32x4;
 typedef __attribute__((ext_vector_type(16))) float h_f32x16;
 
+// ---- operand streaming of the LDS-DMA kernels (igemm_kernel.h, xconv.hip, xconv2.hip, xconv_bs.hip) ----------------------
+typedef __attribute__((address_space(3))) void* h_lds_ptr;
+// LDS-DMA: 64 lanes x 16 bytes from buffer offset (voff per lane + soff) to lds + 16*lane (lds wave-uniform).
+// Kept in a NON-template function: with the builtin inside a kernel template, hipcc (ROCm 7.2) emits no host
+// stub for the instantiations.
+__device__ __forceinline__ void h_dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds, int voff, int soff)
+{
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (h_lds_ptr)lds, 16, voff, soff, 0, 0);
+}
+// LDS image of a [rows][128 B] slab tile, the same in all of these kernels: 16-byte chunk c of row r lives at chunk
+// c ^ ((r >> 1) & 7).  A ds_read_b128 fragment read (16 lanes = 16 distinct rows of a 32-row fragment, same logical chunk) then
+// covers all sixteen 16-byte slots of the 256-byte bank row: conflict free.
+__device__ __forceinline__ int h_lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
+
 // 16-byte store of an output row segment.  HIAST_NT (default 1; -DHIAST_NT=0 for an A/B build of a translation unit): as a
 // NON-TEMPORAL (streaming) store.  Every activation tensor of the trunk is larger than the 32 MiB of L2 and is read next by
 // another kernel (from HBM / the Infinity Cache either way), so keeping its lines dirty in the L2 only (a) evicts the weight /

@@ -186,8 +186,17 @@ __global__ __launch_bounds__(256) void from_planes_kernel(const unsigned short* 
 
 }  // namespace hiast
 
-// tuning variables of the tile kernel, read once per process; the co-scheduling hint of the calling thread (igemm_kernel.h)
-const IgEnv& hiast_ig_env()
+// Tuning variables of the tile kernel, read ONCE per process: a value that changes between a row-count call and the launch would
+// size a statistics buffer for one tile form and run the other.
+// HIAST_IGEMM_HALF=0 / 1: never / every 1x1 launch with N % 128 == 0 on 128 x 128 tiles (A/B and tests); unset: the HBM-bound
+// shapes measured faster (profiles/r05_ab_igemm_half_tile.txt).
+struct IgEnv {
+    int half;        // HIAST_IGEMM_HALF: -1 unset | 0 | 1
+    int bn;          // HIAST_IGEMM_BN: 0 unset | 64 | 128 | 256
+    int ragged_off;  // HIAST_IGEMM_RAGGED set: no ragged 256-column tiles for the plain N = 640 GEMM
+    int cosched0;    // HIAST_IGEMM_COSCHED: the process default of the co-scheduling hint
+};
+static const IgEnv& ig_env()
 {
     static const IgEnv env = [] {
         IgEnv e;
@@ -203,9 +212,11 @@ const IgEnv& hiast_ig_env()
     }();
     return env;
 }
+// The hints of the calling thread (include/hiast_hip.h).  Co-scheduling: "this thread runs two launch sequences side by side" —
+// two half-chip launches on two streams already fill the chip, so they keep the 256-row form.  THREAD-LOCAL state (-1 = the
+// process default above), never the environment: setenv / unsetenv around every forward raced with getenv in other threads
+// (ADVICE r5).
 static thread_local int ig_cosched_tls = -1, ig_half_tls = -1;
-int hiast_ig_cosched_tls_get() { return ig_cosched_tls; }
-int hiast_ig_half_tls_get() { return ig_half_tls; }
 extern "C" int hiast_igemm_set_half(int v)
 {
     const int prev = ig_half_tls;
@@ -218,99 +229,133 @@ extern "C" int hiast_igemm_set_cosched(int on)
     ig_cosched_tls = on < 0 ? -1 : (on != 0);
     return prev;
 }
+static int ig_half_forced() { return ig_half_tls >= 0 ? ig_half_tls : ig_env().half; }
+static int ig_cosched() { return ig_cosched_tls >= 0 ? ig_cosched_tls : ig_env().cosched0; }
 
-// K9e (xconv.hip): register-resident-weight kernel for the HBM-bound expanding 1x1 shapes
-int hiast_xconv_ok(int64_t M, int K, int N, int planes, int taps, int out_f32, int has_bn, int has_res, int relu,
-                   int has_gate, int gate_mask, int has_stats);
-int hiast_xconv_stats_rows(int64_t M, int N);
-int hiast_xconv_launch(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                       const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N,
-                       float* stats, const void* res_gate, int f16, hipStream_t st);
-// K9g (xconv2.hip): the same idea for the split-plane 256 -> N launches with BatchNorm(eval) (+ residual + ReLU)
-int hiast_xconv2_ok(int64_t M, int K, int N, int planes, int taps, int out_f32, int has_bn, int has_res, int relu,
-                    int has_gate, int has_stats);
-int hiast_xconv2_launch(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                        const float* var, float eps, const void* res, int relu, void* y, int64_t M, int N, hipStream_t st);
-// igemm_f16.hip: the fp16 instantiations of the tile kernel (a translation unit of its own: build time)
-int hiast_igemm_launch_f16(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                           const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N, int taps,
-                           hiast::IGeo geo, float* stats, const void* res_gate, int gate_mask, hipStream_t st, int stats_mode,
-                           int out_f32, int stats_rows);
-
-// stats_mode: 0 none, 1 forward BatchNorm sums of the output (stats), 2 backward BatchNorm sums of the activation whose
-// gradient the output is (data-gradient launches: res = that BN's input x, mean / var = its batch mean / invstd)
-static int igemm_launch_mode(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                             const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N,
-                             int taps, int H, int W, int stride, int dil, int fmt, int out_f32, hipStream_t st,
-                             float* stats, const void* res_gate, int gate_mask, int stats_mode, int stats_rows)
+// automatic choice of the 128 x 128 / two-blocks-per-CU form (ig_half_tile below); M pixels, K -> N channels, 1x1 only
+// Measured (profiles/r05_ab_igemm_half_tile.txt): stand-alone the 128 x 128 form wins wherever the 256-row form leaves half of
+// the chip idle (<= 128 blocks: the 1024 -> 256 launch of a 4-image batch 71 -> 53 us in split planes, 38 -> 32 us in fp16) and
+// loses 5-12 % where the 256-row form fills the chip once (B = 8: 50 -> 55 us; the operands pass the L2 -> LDS path twice).
+// In the step the 4-image launches are the two sub-batches of an inference forward on two streams — two half-chip launches
+// side by side already fill the chip, and the step did not move (55.5 / 55.5 against 55.7 / 55.8 ms) — so the automatic rule takes
+// the quarter-chip launches only (<= 64 blocks): the pseudo-label generator at the reference's batch size 2 runs 247 -> 271
+// images/s end to end with it.
+#ifndef IG_HALF_AUTO
+#define IG_HALF_BLOCKS(M, N) ((((M) + 255) / 256) * (((N) % 256 == 0) ? (N) / 256 : (N) / 128))
+// (half-chip launches too — unless the caller runs two launch sequences side by side: HIAST_IGEMM_COSCHED=1, set by
+// functional.eval_forward_split around its sub-batches; two half-chip launches on two streams already fill the chip)
+#define IG_HALF_AUTO(M, K, N) (IG_HALF_BLOCKS(M, N) <= 64 || (IG_HALF_BLOCKS(M, N) <= 128 && !ig_cosched()))
+#endif
+// does this launch run on 128 x 128 tiles, two 4-wave blocks per CU (igemm_kernel.h BM = 128)?
+static int ig_half_tile(int64_t M, int K, int N, int taps, int out_f32)
 {
-    if (!hiast_fmt_ok(fmt)) return HIAST_E_RANGE;
-    const int planes = hiast_fmt_planes(fmt), f16 = fmt == HIAST_FMT_FP16;
-    if (stats_mode == 2) {
-        if (!stats || !res || !mean || !var || planes != 1 || out_f32 || relu || res_gate || N % 8) return HIAST_E_RANGE;
-    } else {
-        if (stats && (planes != 1 || out_f32 || res || relu)) return HIAST_E_RANGE;
-        if ((stats || res_gate) && mean) return HIAST_E_RANGE;   // the statistics / gradient variants carry no BatchNorm
-    }
-    if (res_gate && (planes != 1 || !res || relu || out_f32 || (!gate_mask && (((uintptr_t)res_gate) & 15)))) return HIAST_E_RANGE;
-    if (!x || !wp || !y || (mean && !var)) return HIAST_E_ARG;
-    if (M <= 0 || K <= 0 || N <= 0) return HIAST_E_ARG;
-    if ((planes != 1 && planes != 2) || (taps != 1 && taps != 9)) return HIAST_E_RANGE;
-    if ((K * planes) % 64 != 0 || N % 64 != 0 || M > (1ll << 31) - 512) return HIAST_E_RANGE;
-    if (out_f32 && res) return HIAST_E_RANGE;
-    if ((((uintptr_t)x) | ((uintptr_t)wp) | ((uintptr_t)y) | ((uintptr_t)res)) & 15) return HIAST_E_RANGE;
-    hiast::IGeo geo = {0, 0, 0, 0, 1, 1};
-    size_t in_pix = (size_t)M;
-    if (taps != 1 && stride == -2) {
-        // transposed stride-2 3x3 (hiast_igemm_dgrad_s2): H x W is the OUTPUT map (the strided convolution's input), the
-        // operand rows are its output gradient on ((H-1)/2+1) x ((W-1)/2+1)
-        if (H <= 0 || W <= 0 || dil != 1 || planes != 1 || out_f32) return HIAST_E_ARG;
-        const int Hs = (H - 1) / 2 + 1, Ws = (W - 1) / 2 + 1;
-        if (M % ((int64_t)H * W) != 0) return HIAST_E_ARG;
-        geo = {Hs, Ws, H, W, -2, 1};
-        in_pix = (size_t)(M / ((int64_t)H * W)) * Hs * Ws;
-    } else if (taps != 1) {
-        if (H <= 0 || W <= 0 || stride <= 0 || dil <= 0) return HIAST_E_ARG;
-        const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-        if (M % ((int64_t)Ho * Wo) != 0) return HIAST_E_ARG;
-        geo = {H, W, Ho, Wo, stride, dil};
-        in_pix = (size_t)(M / ((int64_t)Ho * Wo)) * H * W;
-    }
-    // buffer-descriptor addressing: byte offsets and the out-of-range marker need 31 bits
-    if (in_pix * planes * K * 2 >= (1ull << 31) || (size_t)N * taps * planes * K * 2 >= (1ull << 31)) return HIAST_E_RANGE;
-    if (stats_mode != 2 &&
-        hiast_xconv_ok(M, K, N, planes, taps, out_f32, mean != nullptr, res != nullptr, relu, res_gate != nullptr, gate_mask,
-                       stats != nullptr)) {
-        if (stats && stats_rows != hiast_xconv_stats_rows(M, N)) return HIAST_E_ARG;
-        return hiast_xconv_launch(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, stats, res_gate, f16, st);
-    }
-    if (stats_mode == 0 && !f16 &&
-        hiast_xconv2_ok(M, K, N, planes, taps, out_f32, mean != nullptr, res != nullptr, relu, res_gate != nullptr, stats != nullptr))
-        return hiast_xconv2_launch(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, N, st);
-    if (f16)
-        return hiast_igemm_launch_f16(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, geo, stats, res_gate,
-                                      gate_mask, st, stats_mode, out_f32, stats_rows);
-    if (planes == 2) {
-        if (out_f32) return launch_igemm_t<2, true>(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, geo, stats, res_gate, gate_mask, st, stats_mode, stats_rows);
-        return launch_igemm_t<2, false>(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, geo, stats, res_gate, gate_mask, st, stats_mode, stats_rows);
-    }
-    if (out_f32) return launch_igemm_t<1, true>(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, geo, stats, res_gate, gate_mask, st, stats_mode, stats_rows);
-    return launch_igemm_t<1, false>(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, geo, stats, res_gate, gate_mask, st, stats_mode, stats_rows);
+    // (1x1 only: on the 3x3 launches the form was measured 20-25 % slower wherever the 256-row form fills the chip — twice the
+    // L2 -> LDS bytes and a third more fragment reads per flop in an MFMA-bound loop — profiles/r05_ab_igemm_half_tile.txt)
+    if (taps != 1 || out_f32 || N % 128 != 0 || M < 4096) return 0;
+    if (ig_half_forced() >= 0) return ig_half_forced();
+    return IG_HALF_AUTO(M, K, N);
+}
+// ... and the split-plane 3x3 + BN + ReLU launch of the pseudo-label forward in the same form when its 256-row form fills at most a
+// quarter of the chip (the generator at the reference's batch size 2: 64 tiles): stand-alone 144 -> 103 us already at 4 images
+// (profiles/r05_ab_igemm_half_tile.txt); on full-chip launches the form is 20-25 % slower, so never there.
+static int ig_half_tile9(int64_t M, int N, int PL, bool bn_relu_only)
+{
+    if (PL != 2 || !bn_relu_only || N % 128 != 0 || M < 4096) return 0;
+    if (ig_half_forced() >= 0) return ig_half_forced();
+    return IG_HALF_AUTO(M, 0, N);
 }
 
-// shared launcher (also used by aspp2.hip for the ASPP tap GEMM)
-int hiast_igemm_launch(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                       const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N,
-                       int taps, int H, int W, int stride, int dil, int fmt, int out_f32, hipStream_t st,
-                       float* stats, const void* res_gate, int gate_mask, int stats_rows)
+// Which kernel takes this launch, in which form, and how many block rows it writes: the ONE place that decides it.
+// hiast_igemm_launch launches what this returns; the row-count entries of the ABI read `rows` from it.
+ConvRoute ig_route(const ConvLaunch& c)
 {
-    return igemm_launch_mode(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, H, W, stride, dil, fmt,
-                             out_f32, st, stats, res_gate, gate_mask, stats ? 1 : 0, stats_rows);
+    ConvRoute r;
+    if (c.stats_mode != 2 && hiast_xconv_ok(c)) {
+        r.family = ConvFamily::XCONV;
+        r.rows = hiast_xconv_stats_rows(c.M, c.N);
+        return r;
+    }
+    if (c.stats_mode == 0 && !c.f16() && hiast_xconv2_ok(c)) {
+        r.family = ConvFamily::XCONV2;
+        return r;
+    }
+    r.family = c.f16() ? ConvFamily::TILE_F16 : ConvFamily::TILE;
+    r.BN = (c.N % 256 == 0) ? 256 : ((c.N % 128 == 0) ? 128 : 64);
+    // a plain GEMM (no BN / residual / ReLU / gate / statistics) of N = 2.5, 3.5, ... tiles of 256 runs on 256-column tiles
+    // with the last one hanging over N (zero weight rows from the buffer rule, no stores): the ASPP tap GEMM, N = 640, 16-bit
+    // output — 0.170 against 0.181 ms on five 128-column tiles although a fifth of the last tile's MFMAs multiply zeros (with
+    // fp32 output the 128-column tiles win: 0.187 against 0.197)
+    const bool plain = !c.mean && !c.gamma && !c.res && !c.relu && !c.res_gate && c.stats_mode == 0;
+    if (plain && !c.out_f32 && r.BN == 128 && c.N > 512 && !ig_env().ragged_off) r.BN = 256;
+    if (const int v = ig_env().bn) {                            // tuning override (HIAST_IGEMM_BN)
+        if (c.N % v == 0) r.BN = v;
+    }
+    r.half9 = c.taps == 9 && !c.out_f32 && c.geo.stride == 1 &&
+              ig_half_tile9(c.M, c.N, c.planes(), c.mean && c.relu && !c.res && !c.res_gate && c.stats_mode == 0) != 0;
+    const bool half = r.half9 || (c.geo.stride >= 0 && ig_half_tile(c.M, c.K, c.N, c.taps, c.out_f32) != 0);
+    if (half) r.BN = 128;
+    r.BM = half ? 128 : hiast::IG_BM;
+    r.rows = (int)((c.M + r.BM - 1) / r.BM);
+    return r;
+}
+
+// Validates, routes and launches (hiast_igemm_bn_act, the data-gradient entries below, aspp2.hip's tap GEMMs).  The caller's
+// c.geo carries H, W, stride and dil as the ABI states them; the derived maps are filled in here.
+int hiast_igemm_launch(const ConvLaunch& in)
+{
+    ConvLaunch c = in;
+    if (c.stats_mode != 2) c.stats_mode = c.stats ? 1 : 0;
+    const int H = c.geo.H, W = c.geo.W, stride = c.geo.stride, dil = c.geo.dil;
+    if (!hiast_fmt_ok(c.fmt)) return HIAST_E_RANGE;
+    const int planes = c.planes();
+    if (c.stats_mode == 2) {
+        if (!c.stats || !c.res || !c.mean || !c.var || planes != 1 || c.out_f32 || c.relu || c.res_gate || c.N % 8) return HIAST_E_RANGE;
+    } else {
+        if (c.stats && (planes != 1 || c.out_f32 || c.res || c.relu)) return HIAST_E_RANGE;
+        if ((c.stats || c.res_gate) && c.mean) return HIAST_E_RANGE;   // the statistics / gradient variants carry no BatchNorm
+    }
+    if (c.res_gate && (planes != 1 || !c.res || c.relu || c.out_f32 || (!c.gate_mask && (((uintptr_t)c.res_gate) & 15)))) return HIAST_E_RANGE;
+    if (!c.x || !c.wp || !c.y || (c.mean && !c.var)) return HIAST_E_ARG;
+    if (c.M <= 0 || c.K <= 0 || c.N <= 0) return HIAST_E_ARG;
+    if ((planes != 1 && planes != 2) || (c.taps != 1 && c.taps != 9)) return HIAST_E_RANGE;
+    if ((c.K * planes) % 64 != 0 || c.N % 64 != 0 || c.M > (1ll << 31) - 512) return HIAST_E_RANGE;
+    if (c.out_f32 && c.res) return HIAST_E_RANGE;
+    if ((((uintptr_t)c.x) | ((uintptr_t)c.wp) | ((uintptr_t)c.y) | ((uintptr_t)c.res)) & 15) return HIAST_E_RANGE;
+    c.geo = {0, 0, 0, 0, 1, 1};
+    size_t in_pix = (size_t)c.M;
+    if (c.taps != 1 && stride == -2) {
+        // transposed stride-2 3x3 (hiast_igemm_dgrad_s2): H x W is the OUTPUT map (the strided convolution's input), the
+        // operand rows are its output gradient on ((H-1)/2+1) x ((W-1)/2+1)
+        if (H <= 0 || W <= 0 || dil != 1 || planes != 1 || c.out_f32) return HIAST_E_ARG;
+        const int Hs = (H - 1) / 2 + 1, Ws = (W - 1) / 2 + 1;
+        if (c.M % ((int64_t)H * W) != 0) return HIAST_E_ARG;
+        c.geo = {Hs, Ws, H, W, -2, 1};
+        in_pix = (size_t)(c.M / ((int64_t)H * W)) * Hs * Ws;
+    } else if (c.taps != 1) {
+        if (H <= 0 || W <= 0 || stride <= 0 || dil <= 0) return HIAST_E_ARG;
+        const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+        if (c.M % ((int64_t)Ho * Wo) != 0) return HIAST_E_ARG;
+        c.geo = {H, W, Ho, Wo, stride, dil};
+        in_pix = (size_t)(c.M / ((int64_t)Ho * Wo)) * H * W;
+    }
+    // buffer-descriptor addressing: byte offsets and the out-of-range marker need 31 bits
+    if (in_pix * planes * c.K * 2 >= (1ull << 31) || (size_t)c.N * c.taps * planes * c.K * 2 >= (1ull << 31)) return HIAST_E_RANGE;
+    const ConvRoute r = ig_route(c);
+    // the statistics epilogues write one row of sums per block row of THIS route: the caller's buffer has to be that long
+    if (c.stats_mode != 0 && c.stats_rows != r.rows) return HIAST_E_ARG;
+    switch (r.family) {
+    case ConvFamily::XCONV: return hiast_xconv_launch(c, r);
+    case ConvFamily::XCONV2: return hiast_xconv2_launch(c);
+    case ConvFamily::TILE_F16: return hiast_igemm_launch_f16(c, r);
+    case ConvFamily::TILE: break;
+    }
+    if (planes == 2) return c.out_f32 ? launch_igemm_t<2, true>(c, r) : launch_igemm_t<2, false>(c, r);
+    return c.out_f32 ? launch_igemm_t<1, true>(c, r) : launch_igemm_t<1, false>(c, r);
 }
 
 // Data gradient of a stride-1 trunk convolution (dy x the adjoint weight, hiast_pack_conv_weight transpose) whose output
 // dA is the gradient of A = relu(bn(x)): also emits the per-block sums (Σg, Σ g*xhat) of that BatchNorm's backward,
-// partial[hiast_igemm_stats_rows][Cout][2] — hiast_bn_nhwc_stats_from_partial turns them into the sums that
+// partial[hiast_igemm_dgrad_bn_stats_rows][Cout][2] — hiast_bn_nhwc_stats_from_partial turns them into the sums that
 // hiast_bn_nhwc_bwd_apply takes (reference: autograd of conv -> bn -> relu in Bottleneck.forward, resnet.py:78-98).
 extern "C" int hiast_igemm_dgrad_bn_stats(const void* dy, const void* wpt, void* da, int B, int H, int W, int Cin, int Cout,
                                           int taps, int dil, const void* bn_x, const float* gamma, const float* beta,
@@ -321,8 +366,15 @@ extern "C" int hiast_igemm_dgrad_bn_stats(const void* dy, const void* wpt, void*
     if (B <= 0 || H <= 0 || W <= 0) return HIAST_E_ARG;
     if (!bn_x || !save_mean || !save_invstd || !partial) return HIAST_E_ARG;
     if ((((uintptr_t)save_mean) | ((uintptr_t)save_invstd) | ((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) return HIAST_E_RANGE;
-    return igemm_launch_mode(dy, wpt, gamma, beta, save_mean, save_invstd, 0.0f, bn_x, 0, da, (int64_t)B * H * W, Cin, Cout,
-                             taps, H, W, 1, dil, fmt, 0, (hipStream_t)stream, partial, nullptr, 0, 2, partial_rows);
+    ConvLaunch c;
+    c.x = dy; c.wp = wpt; c.y = da; c.res = bn_x;
+    c.gamma = gamma; c.beta = beta; c.mean = save_mean; c.var = save_invstd;
+    c.M = (int64_t)B * H * W; c.K = Cin; c.N = Cout; c.taps = taps;
+    c.geo.H = H; c.geo.W = W; c.geo.dil = dil;
+    c.fmt = fmt;
+    c.stats = partial; c.stats_rows = partial_rows; c.stats_mode = 2;
+    c.st = (hipStream_t)stream;
+    return hiast_igemm_launch(c);
 }
 
 // Data gradient of a 3x3 / stride-2 / padding-1 trunk convolution (layer2.0.conv2; autograd of that nn.Conv2d in
@@ -333,16 +385,13 @@ extern "C" int hiast_igemm_dgrad_s2(const void* dy, const void* wpt, void* dx, i
 {
     if (fmt != HIAST_FMT_BF16 && fmt != HIAST_FMT_FP16) return HIAST_E_RANGE;
     if (B <= 0 || H <= 0 || W <= 0) return HIAST_E_ARG;
-    return igemm_launch_mode(dy, wpt, nullptr, nullptr, nullptr, nullptr, 0.0f, nullptr, 0, dx, (int64_t)B * H * W, Cout, Cin, 9,
-                             H, W, -2, 1, fmt, 0, (hipStream_t)stream, nullptr, nullptr, 0, 0, 0);
-}
-
-// rows of the partial-sum buffer of hiast_igemm_dgrad_bn_stats: one per block row of the tile form the launch takes
-extern "C" int hiast_igemm_dgrad_bn_stats_rows(int64_t M, int Cin, int Cout, int taps)
-{
-    if (M <= 0) return 0;
-    const int bm = ig_block_rows(M, Cin, Cout, taps, 0);
-    return (int)((M + bm - 1) / bm);
+    ConvLaunch c;
+    c.x = dy; c.wp = wpt; c.y = dx;
+    c.M = (int64_t)B * H * W; c.K = Cout; c.N = Cin; c.taps = 9;
+    c.geo.H = H; c.geo.W = W; c.geo.stride = -2;
+    c.fmt = fmt;
+    c.st = (hipStream_t)stream;
+    return hiast_igemm_launch(c);
 }
 
 extern "C" int hiast_igemm_bn_act(const void* x, const void* wp, const float* gamma, const float* beta,
@@ -354,8 +403,36 @@ extern "C" int hiast_igemm_bn_act(const void* x, const void* wp, const float* ga
     if (B <= 0 || H <= 0 || W <= 0) return HIAST_E_ARG;
     if (taps == 1 && stride != 1) return HIAST_E_RANGE;       // strided 1x1: subsample the input first
     const int Ho = taps == 1 ? H : (H - 1) / stride + 1, Wo = taps == 1 ? W : (W - 1) / stride + 1;
-    return hiast_igemm_launch(x, wp, gamma, beta, mean, var, eps, res, relu, y, (int64_t)B * Ho * Wo, Cin, Cout, taps, H,
-                              W, stride, dil, fmt, out_f32, (hipStream_t)stream, stats, res_gate, gate_mask, stats_rows);
+    ConvLaunch c;
+    c.x = x; c.wp = wp; c.y = y; c.res = res; c.res_gate = res_gate; c.gate_mask = gate_mask;
+    c.gamma = gamma; c.beta = beta; c.mean = mean; c.var = var; c.eps = eps;
+    c.relu = relu;
+    c.M = (int64_t)B * Ho * Wo; c.K = Cin; c.N = Cout; c.taps = taps;
+    c.geo.H = H; c.geo.W = W; c.geo.stride = stride; c.geo.dil = dil;
+    c.fmt = fmt; c.out_f32 = out_f32;
+    c.stats = stats; c.stats_rows = stats_rows;
+    c.st = (hipStream_t)stream;
+    return hiast_igemm_launch(c);
+}
+
+// Rows of the partial-sum buffers: the `rows` of the route that the launch they size takes.  A want_stats launch is always the
+// PLAIN convolution (hiast_igemm_launch refuses stats together with a BatchNorm, a residual or a ReLU), the backward-statistics
+// launch always has its BatchNorm and its residual rows; neither presence changes the form of either launch.
+extern "C" int hiast_igemm_stats_rows(int64_t M, int Cin, int Cout, int taps, int fmt)
+{
+    if (M <= 0 || Cin <= 0 || Cout <= 0) return 0;
+    ConvLaunch c;
+    c.M = M; c.K = Cin; c.N = Cout; c.taps = taps; c.fmt = fmt;
+    c.stats_mode = 1;
+    return ig_route(c).rows;
+}
+extern "C" int hiast_igemm_dgrad_bn_stats_rows(int64_t M, int Cin, int Cout, int taps)
+{
+    if (M <= 0) return 0;
+    ConvLaunch c;
+    c.M = M; c.K = Cin; c.N = Cout; c.taps = taps;
+    c.stats_mode = 2;
+    return ig_route(c).rows;
 }
 
 #ifdef IG_STAMP
@@ -371,18 +448,6 @@ extern "C" int hiast_igemm_debug_stamps(unsigned* dst_device)
     return (int)hipDeviceSynchronize();
 }
 #endif
-
-// rows of the partial-sum buffer of a want_stats launch.  Such a launch is always the PLAIN convolution: igemm_launch_mode
-// rejects stats together with a BatchNorm, a residual or a ReLU (HIAST_E_RANGE), so the kernel choice below (xconv for the
-// expanding 1x1 shapes, the tile kernel otherwise) is the one the launch makes.
-extern "C" int hiast_igemm_stats_rows(int64_t M, int Cin, int Cout, int taps, int fmt)
-{
-    const int planes = hiast_fmt_planes(fmt);
-    if (M <= 0 || Cin <= 0 || Cout <= 0) return 0;
-    if (hiast_xconv_ok(M, Cin, Cout, planes, taps, 0, 0, 0, 0, 0, 0, 1)) return hiast_xconv_stats_rows(M, Cout);
-    const int bm = ig_block_rows(M, Cin, Cout, taps, 0);
-    return (int)((M + bm - 1) / bm);
-}
 
 extern "C" int hiast_pack_conv_weight(const float* w, int N, int K, int taps, int fmt, int transpose, void* wp,
                                       void* wpt, hiast_stream_t stream)

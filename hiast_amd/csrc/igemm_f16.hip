@@ -4,14 +4,7 @@
 // Same kernel text as the bf16 variants (LDS-DMA slabs, asm fragment reads, counted waits); only H16<true> differs.
 #include "igemm_kernel.h"
 
-int hiast_igemm_launch_f16(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                           const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N, int taps,
-                           hiast::IGeo geo, float* stats, const void* res_gate, int gate_mask, hipStream_t st, int stats_mode,
-                           int out_f32, int stats_rows)
+int hiast_igemm_launch_f16(const ConvLaunch& c, const ConvRoute& r)
 {
-    if (out_f32)
-        return launch_igemm_t<1, true, true>(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, geo, stats,
-                                             res_gate, gate_mask, st, stats_mode, stats_rows);
-    return launch_igemm_t<1, false, true>(x, wp, gamma, beta, mean, var, eps, res, relu, y, M, K, N, taps, geo, stats,
-                                          res_gate, gate_mask, st, stats_mode, stats_rows);
+    return c.out_f32 ? launch_igemm_t<1, true, true>(c, r) : launch_igemm_t<1, false, true>(c, r);
 }

@@ -40,13 +40,9 @@
 #include <hip/hip_bf16.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_launch.h"
 
 namespace hiast {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 ig_bf16x8;
-typedef __attribute__((ext_vector_type(16))) float ig_f32x16;
-typedef __attribute__((ext_vector_type(4))) float ig_f32x4;
 
 constexpr int IG_BM = 256;
 // which launches run the early-barrier k-loop (igemm_bn_act_kernel): a compile-time choice per (planes, taps).  Measured
@@ -58,20 +54,6 @@ constexpr int IG_BM = 256;
 #endif
 #ifndef IG_FLIP8
 #define IG_FLIP8 4
-#endif
-// automatic choice of the 128 x 128 / two-blocks-per-CU form (ig_half_tile below); M pixels, K -> N channels, 1x1 only
-// Measured (profiles/r05_ab_igemm_half_tile.txt): stand-alone the 128 x 128 form wins wherever the 256-row form leaves half of
-// the chip idle (<= 128 blocks: the 1024 -> 256 launch of a 4-image batch 71 -> 53 us in split planes, 38 -> 32 us in fp16) and
-// loses 5-12 % where the 256-row form fills the chip once (B = 8: 50 -> 55 us; the operands pass the L2 -> LDS path twice).
-// In the step the 4-image launches are the two sub-batches of an inference forward on two streams — two half-chip launches
-// side by side already fill the chip, and the step did not move (55.5 / 55.5 against 55.7 / 55.8 ms) — so the automatic rule takes
-// the quarter-chip launches only (<= 64 blocks): the pseudo-label generator at the reference's batch size 2 runs 247 -> 271
-// images/s end to end with it.
-#ifndef IG_HALF_AUTO
-#define IG_HALF_BLOCKS(M, N) ((((M) + 255) / 256) * (((N) % 256 == 0) ? (N) / 256 : (N) / 128))
-// (half-chip launches too — unless the caller runs two launch sequences side by side: HIAST_IGEMM_COSCHED=1, set by
-// functional.eval_forward_split around its sub-batches; two half-chip launches on two streams already fill the chip)
-#define IG_HALF_AUTO(M, K, N) (IG_HALF_BLOCKS(M, N) <= 64 || (IG_HALF_BLOCKS(M, N) <= 128 && !ig_cosched()))
 #endif
 
 #ifdef IG_STAMP       // diagnostic build (tools/igemm_stamps.py): cycles a wave spends in the parts of a k-step, summed over the loop
@@ -89,15 +71,6 @@ __device__ __forceinline__ unsigned ig_now()
 #define IG_ACC(i, a, b)
 #endif
 
-struct IGeo {
-    int H, W, Ho, Wo, stride, dil;
-};
-
-// LDS image of a [rows][128 B] tile: 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7).  A ds_read_b128
-// fragment read (16 lanes = 16 distinct rows of a 32-row fragment, same logical chunk) then covers all sixteen
-// 16-byte slots of the 256-byte bank row: conflict free.
-__device__ __forceinline__ int ig_lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
 __device__ __forceinline__ void ig_split(float v, unsigned short& h, unsigned short& l)
 {
     const __hip_bfloat16 hb = __float2bfloat16(v);
@@ -105,43 +78,34 @@ __device__ __forceinline__ void ig_split(float v, unsigned short& h, unsigned sh
     l = __bfloat16_as_ushort(__float2bfloat16(v - __bfloat162float(hb)));
 }
 
-typedef __attribute__((address_space(3))) void* ig_lds_ptr;
-
-// LDS-DMA: 64 lanes x 16 bytes from buffer offset (voff per lane + soff) to lds + 16*lane (lds wave-uniform).
-// Kept in a NON-template function: with the builtin inside a kernel template, hipcc (ROCm 7.2) emits no host
-// stub for the instantiations.
-__device__ __forceinline__ void ig_dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds, int voff, int soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (ig_lds_ptr)lds, 16, voff, soff, 0, 0);
-}
-// ... with the non-temporal cache policy (aux bit 1 = nt): the A operand of a 1x1 launch is read exactly ONCE, by one block
+// h_dma16 (common.h) with the non-temporal cache policy (aux bit 1 = nt): the A operand of a 1x1 launch is read exactly ONCE, by one block
 // (IG_A_NT: A/B build, tools/build_variant_igemm.sh ... -DIG_A_NT=1)
 #ifndef IG_A_NT
 #define IG_A_NT 0
 #endif
 __device__ __forceinline__ void ig_dma16_nt(__amdgpu_buffer_rsrc_t rs, unsigned char* lds, int voff, int soff)
 {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (ig_lds_ptr)lds, 16, voff, soff, 0, IG_A_NT ? 2 : 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (h_lds_ptr)lds, 16, voff, soff, 0, IG_A_NT ? 2 : 0);
 }
 
 // Fragment reads as inline asm (ds_read_b128, tile offset as the instruction's immediate) with explicit lgkmcnt waits that
 // tie the destination registers: the compiler orders every LDS load it can see behind ALL pending LDS-DMAs
 // (s_waitcnt vmcnt(0)), which would make the DMA of k-step t+1 a wait inside k-step t.
 template <int OFF>
-__device__ __forceinline__ ig_bf16x8 ig_lds_read(unsigned addr)
+__device__ __forceinline__ h_bf16x8 ig_lds_read(unsigned addr)
 {
-    ig_bf16x8 v;
+    h_bf16x8 v;
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
     return v;
 }
-__device__ __forceinline__ void ig_lds_read4(ig_bf16x8 (&f)[4][2], unsigned addr)       // B: four 16-row tiles x two chunks
+__device__ __forceinline__ void ig_lds_read4(h_bf16x8 (&f)[4][2], unsigned addr)       // B: four 16-row tiles x two chunks
 {
     f[0][0] = ig_lds_read<0>(addr);        f[0][1] = ig_lds_read<0>(addr ^ 64u);
     f[1][0] = ig_lds_read<2048>(addr);     f[1][1] = ig_lds_read<2048>(addr ^ 64u);
     f[2][0] = ig_lds_read<4096>(addr);     f[2][1] = ig_lds_read<4096>(addr ^ 64u);
     f[3][0] = ig_lds_read<6144>(addr);     f[3][1] = ig_lds_read<6144>(addr ^ 64u);
 }
-__device__ __forceinline__ void ig_lds_read_b(ig_bf16x8 (&f)[2], unsigned addr, int b)  // B: 16-row tile b (a constant after unrolling)
+__device__ __forceinline__ void ig_lds_read_b(h_bf16x8 (&f)[2], unsigned addr, int b)  // B: 16-row tile b (a constant after unrolling)
 {
     switch (b) {
     case 1: f[0] = ig_lds_read<2048>(addr); f[1] = ig_lds_read<2048>(addr ^ 64u); break;
@@ -150,7 +114,7 @@ __device__ __forceinline__ void ig_lds_read_b(ig_bf16x8 (&f)[2], unsigned addr, 
     default: f[0] = ig_lds_read<0>(addr); f[1] = ig_lds_read<0>(addr ^ 64u); break;
     }
 }
-__device__ __forceinline__ void ig_lds_read_a(ig_bf16x8 (&f)[2], unsigned addr, int a)  // A: 16-row tile a (a is a constant
+__device__ __forceinline__ void ig_lds_read_a(h_bf16x8 (&f)[2], unsigned addr, int a)  // A: 16-row tile a (a is a constant
 {                                                                                        // after unrolling)
     switch (a) {
     case 1: f[0] = ig_lds_read<1 * 2048>(addr); f[1] = ig_lds_read<1 * 2048>(addr ^ 64u); break;
@@ -164,20 +128,20 @@ __device__ __forceinline__ void ig_lds_read_a(ig_bf16x8 (&f)[2], unsigned addr, 
     }
 }
 template <int N>
-__device__ __forceinline__ void ig_lds_wait_n(ig_bf16x8 (&f)[2], ig_bf16x8 (&g)[2])    // all but the N youngest LDS reads are done
+__device__ __forceinline__ void ig_lds_wait_n(h_bf16x8 (&f)[2], h_bf16x8 (&g)[2])    // all but the N youngest LDS reads are done
 {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(f[0]), "+v"(f[1]), "+v"(g[0]), "+v"(g[1]) : "n"(N));
 }
 template <int N>
-__device__ __forceinline__ void ig_lds_wait_n(ig_bf16x8 (&f)[2])
+__device__ __forceinline__ void ig_lds_wait_n(h_bf16x8 (&f)[2])
 {
     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f[0]), "+v"(f[1]) : "n"(N));
 }
-__device__ __forceinline__ void ig_lds_wait_a(ig_bf16x8 (&f)[2])
+__device__ __forceinline__ void ig_lds_wait_a(h_bf16x8 (&f)[2])
 {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]));
 }
-__device__ __forceinline__ void ig_lds_wait_b(ig_bf16x8 (&f)[4][2], ig_bf16x8 (&g)[2])
+__device__ __forceinline__ void ig_lds_wait_b(h_bf16x8 (&f)[4][2], h_bf16x8 (&g)[2])
 {
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(f[0][0]), "+v"(f[0][1]), "+v"(f[1][0]), "+v"(f[1][1]), "+v"(f[2][0]), "+v"(f[2][1]), "+v"(f[3][0]),
@@ -332,25 +296,25 @@ __global__ __launch_bounds__(BM * 2) void igemm_bn_act_kernel(
             voff = ok ? pix * (KS * 128) + achunk[g] : OOB;
         }
 #ifdef IG_SLABMAJOR_A
-        ig_dma16(xrs, smem + sa * A_BYTES + (4 * wave + g) * 1024, voff, TAPS == 1 ? j * (BM * 128) : j * 128);
+        h_dma16(xrs, smem + sa * A_BYTES + (4 * wave + g) * 1024, voff, TAPS == 1 ? j * (BM * 128) : j * 128);
 #else
         if (TAPS == 1) ig_dma16_nt(xrs, smem + sa * A_BYTES + (4 * wave + g) * 1024, voff, j * 128);
-        else ig_dma16(xrs, smem + sa * A_BYTES + (4 * wave + g) * 1024, voff, j * 128);
+        else h_dma16(xrs, smem + sa * A_BYTES + (4 * wave + g) * 1024, voff, j * 128);
 #endif
     };
     auto dma_b = [&](int kt, int sb, int g, bool on) {
         const int j = TAPS == 1 ? kt : kt / TAPS;
         const int tap = TAPS == 1 ? 0 : kt - j * TAPS;
-        ig_dma16(wrs, smem + NSA * A_BYTES + sb * B_BYTES + (BG * wave + g) * 1024, on ? bvoff[g] : OOB,
+        h_dma16(wrs, smem + NSA * A_BYTES + sb * B_BYTES + (BG * wave + g) * 1024, on ? bvoff[g] : OOB,
                  (tap * KS + j) * 128);
     };
 
     constexpr int NA = 2 * TM;                          // 16-row tiles of the wave tile (8 | 4 | 2); 4 column tiles
-    ig_f32x4 acc4[NA][4];
+    h_f32x4 acc4[NA][4];
 #pragma unroll
     for (int a = 0; a < NA; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc4[a][b] = (ig_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 4; ++b) acc4[a][b] = (h_f32x4){0.f, 0.f, 0.f, 0.f};
 
     const int erow = lane >> 3, ec8 = lane & 7;             // epilogue: lane -> (row of an 8-row group, 8-channel group)
     const int nc = n0 + wn * 64 + ec8 * 8;
@@ -416,7 +380,7 @@ __global__ __launch_bounds__(BM * 2) void igemm_bn_act_kernel(
     const unsigned stamp_begin = ig_now();
 #endif
     constexpr int NAe = 2 * TM;
-    auto mfma_tile = [&](ig_bf16x8 (&fa_)[2], ig_bf16x8 (&fb_)[2], ig_f32x4& c) {
+    auto mfma_tile = [&](h_bf16x8 (&fa_)[2], h_bf16x8 (&fb_)[2], h_f32x4& c) {
         if (PL == 2) {      // lo*hi + hi*lo + hi*hi
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_[1], fb_[0], c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa_[0], fb_[1], c, 0, 0, 0);
@@ -444,7 +408,7 @@ __global__ __launch_bounds__(BM * 2) void igemm_bn_act_kernel(
 #pragma unroll
         for (int g = 0; g < BG; ++g) dma_b(1, 1, g, nk > 1);
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        ig_bf16x8 fb[4][2], fa[2][2];
+        h_bf16x8 fb[4][2], fa[2][2];
         fa[0][0] = ig_lds_read<0>(fa0);
         fa[0][1] = ig_lds_read<0>(fa0 ^ 64u);
         ig_lds_read4(fb, fb0);
@@ -583,7 +547,7 @@ __global__ __launch_bounds__(BM * 2) void igemm_bn_act_kernel(
         // (the next tile's reads, the DMA pieces with their address arithmetic) is issued BETWEEN the MFMAs of a tile, in
         // the shadow of the ones already in the pipe.  The first tile starts as soon as A tile 0 and B tile 0 are there
         // (counted lgkmcnt waits: LDS reads return in order, and the loop holds no other LGKM operation).
-        ig_bf16x8 fb[4][2], fa[2][2];
+        h_bf16x8 fb[4][2], fa[2][2];
         fa[0][0] = ig_lds_read<0>(ca);
         fa[0][1] = ig_lds_read<0>(ca ^ 64u);
         ig_lds_read4(fb, cb);
@@ -868,128 +832,57 @@ __global__ __launch_bounds__(BM * 2) void igemm_bn_act_kernel(
 
 }  // namespace hiast
 
-// host: does this launch run on 128 x 128 tiles, two 4-wave blocks per CU (BM = 128 above)?  ONE rule for the launch and for the
-// callers that size the per-block statistics buffers (hiast_igemm_stats_rows, hiast_igemm_dgrad_bn_stats_rows); the launch checks
-// the caller's row count against the form it takes (HIAST_E_ARG on a mismatch).
-// HIAST_IGEMM_HALF=0 / 1: never / every 1x1 launch with N % 128 == 0 (A/B and tests); unset: the HBM-bound shapes measured faster
-// (profiles/r05_ab_igemm_half_tile.txt).  The tuning variables are read ONCE per process (ig_env below): a value that changes
-// between the row-count call and the launch would size `partial` for one tile form and run the other.
-struct IgEnv {
-    int half;        // HIAST_IGEMM_HALF: -1 unset | 0 | 1
-    int bn;          // HIAST_IGEMM_BN: 0 unset | 64 | 128 | 256
-    int ragged_off;  // HIAST_IGEMM_RAGGED set: no ragged 256-column tiles for the plain N = 640 GEMM
-    int cosched0;    // HIAST_IGEMM_COSCHED: the process default of the co-scheduling hint
-};
-const IgEnv& hiast_ig_env();                             // igemm.hip
-// The co-scheduling hint (hiast_igemm_set_cosched, include/hiast_hip.h): "this thread runs two launch sequences side by side" —
-// two half-chip launches on two streams already fill the chip, so they keep the 256-row form.  THREAD-LOCAL state of the calling
-// thread (-1 = the process default above), never the environment: setenv / unsetenv around every forward raced with getenv in
-// other threads.
-int hiast_ig_cosched_tls_get();                          // igemm.hip
-int hiast_ig_half_tls_get();                             // igemm.hip: hiast_igemm_set_half of the calling thread (-1 = HIAST_IGEMM_HALF / automatic)
-static inline int ig_half_forced()
-{
-    const int t = hiast_ig_half_tls_get();
-    return t >= 0 ? t : hiast_ig_env().half;
-}
-static inline int ig_cosched()
-{
-    const int t = hiast_ig_cosched_tls_get();
-    return t >= 0 ? t : hiast_ig_env().cosched0;
-}
-static inline int ig_half_tile(int64_t M, int K, int N, int taps, int out_f32)
-{
-    // (1x1 only: on the 3x3 launches the form was measured 20-25 % slower wherever the 256-row form fills the chip — twice the
-    // L2 -> LDS bytes and a third more fragment reads per flop in an MFMA-bound loop — profiles/r05_ab_igemm_half_tile.txt)
-    if (taps != 1 || out_f32 || N % 128 != 0 || M < 4096) return 0;
-    if (ig_half_forced() >= 0) return ig_half_forced();
-    return IG_HALF_AUTO(M, K, N);
-}
-// ... and the split-plane 3x3 + BN + ReLU launch of the pseudo-label forward in the same form when its 256-row form fills at most a
-// quarter of the chip (the generator at the reference's batch size 2: 64 tiles): stand-alone 144 -> 103 us already at 4 images
-// (profiles/r05_ab_igemm_half_tile.txt); on full-chip launches the form is 20-25 % slower, so never there.
-static inline int ig_half_tile9(int64_t M, int N, int PL, bool bn_relu_only)
-{
-    if (PL != 2 || !bn_relu_only || N % 128 != 0 || M < 4096) return 0;
-    if (ig_half_forced() >= 0) return ig_half_forced();
-    return IG_HALF_AUTO(M, 0, N);
-}
-static inline int ig_block_rows(int64_t M, int K, int N, int taps, int out_f32)
-{
-    return ig_half_tile(M, K, N, taps, out_f32) ? 128 : hiast::IG_BM;
-}
-
+// host: launch the form of the tile kernel that ig_route (igemm.hip) chose for c.  One selection table for the bf16 / split-plane
+// instantiations (igemm.hip) and the fp16 ones (igemm_f16.hip).
 template <int PL, bool OUTF32, bool F16 = false>
-static int launch_igemm_t(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                          const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N,
-                          int taps, hiast::IGeo geo, float* stats, const void* res_gate, int gate_mask, hipStream_t st,
-                          int stats_mode, int stats_rows)
+static int launch_igemm_t(const ConvLaunch& c, const ConvRoute& r)
 {
-    int BN = (N % 256 == 0) ? 256 : ((N % 128 == 0) ? 128 : 64);
-    // a plain GEMM (no BN / residual / ReLU / gate / statistics) of N = 2.5, 3.5, ... tiles of 256 runs on 256-column tiles
-    // with the last one hanging over N (zero weight rows from the buffer rule, no stores): the ASPP tap GEMM, N = 640, 16-bit
-    // output — 0.170 against 0.181 ms on five 128-column tiles although a fifth of the last tile's MFMAs multiply zeros (with
-    // fp32 output the 128-column tiles win: 0.187 against 0.197)
-    const bool plain = !mean && !gamma && !res && !relu && !stats && !res_gate && stats_mode == 0;
-    if (plain && !OUTF32 && BN == 128 && N > 512 && !hiast_ig_env().ragged_off) BN = 256;
-    if (const int v = hiast_ig_env().bn) {                      // tuning override (HIAST_IGEMM_BN)
-        if (N % v == 0) BN = v;
-    }
-    const bool half9 = taps == 9 && !OUTF32 && geo.stride == 1 &&
-                       ig_half_tile9(M, N, PL, mean && relu && !res && !stats && !res_gate && stats_mode == 0) != 0;
-    const bool half = half9 || (geo.stride >= 0 && ig_half_tile(M, K, N, taps, OUTF32 ? 1 : 0) != 0);
-    if (half) BN = 128;
-    const int BMr = half ? 128 : hiast::IG_BM;
-    dim3 grid((unsigned)((M + BMr - 1) / BMr), (N + BN - 1) / BN);
-    const dim3 block((unsigned)(BMr * 2));
-    // the statistics epilogues write one row of sums per block row of THIS tile form: the caller's buffer has to be that long
-    if (stats && stats_rows != (int)grid.x) return HIAST_E_ARG;
-    const int gate = !res_gate ? 0 : (gate_mask ? 2 : 1);
-    if (geo.stride < 0) {                                   // transposed stride-2 3x3 (UPS): plain 16-bit launches only
+    const dim3 grid((unsigned)r.rows, (c.N + r.BN - 1) / r.BN);
+    const dim3 block((unsigned)(r.BM * 2));
+    const int gate = !c.res_gate ? 0 : (c.gate_mask ? 2 : 1);
+#define LK(BNV, T, RES, RELU, G, S, UPS, BMV)                                                                         \
+    hipLaunchKernelGGL((hiast::igemm_bn_act_kernel<PL, OUTF32, BNV, T, RES, RELU, G, S, F16, UPS, BMV>), grid, block, 0, c.st, \
+                       (const unsigned short*)c.x, (const unsigned short*)c.wp, c.gamma, c.beta, c.mean, c.var, c.eps, \
+                       (const unsigned short*)c.res, c.y, (int)c.M, c.K, c.N, c.geo, c.stats, (const unsigned short*)c.res_gate)
+    if (c.geo.stride < 0) {                                 // transposed stride-2 3x3 (UPS): plain 16-bit launches only
         if constexpr (PL == 1 && !OUTF32) {
-            if (taps != 9 || !plain || N % BN != 0) return HIAST_E_RANGE;
-#define LU(BNV)                                                                                                        \
-    hipLaunchKernelGGL((hiast::igemm_bn_act_kernel<PL, OUTF32, BNV, 9, false, false, 0, 0, F16, true>), grid, dim3(512), 0, st, \
-                       (const unsigned short*)x, (const unsigned short*)wp, gamma, beta, mean, var, eps,                \
-                       (const unsigned short*)res, y, (int)M, K, N, geo, stats, (const unsigned short*)res_gate)
-            if (BN == 256) LU(256); else if (BN == 128) LU(128); else LU(64);
-#undef LU
+            const bool plain = !c.mean && !c.gamma && !c.res && !c.relu && !c.res_gate && c.stats_mode == 0;
+            if (c.taps != 9 || !plain || c.N % r.BN != 0) return HIAST_E_RANGE;
+            if (r.BN == 256) LK(256, 9, false, false, 0, 0, true, 256);
+            else if (r.BN == 128) LK(128, 9, false, false, 0, 0, true, 256);
+            else LK(64, 9, false, false, 0, 0, true, 256);
             HIAST_CHECK_LAUNCH();
             return 0;
         } else {
             return HIAST_E_RANGE;
         }
     }
-#define LK(BNV, T, RES, RELU, G, S, BMV)                                                                              \
-    hipLaunchKernelGGL((hiast::igemm_bn_act_kernel<PL, OUTF32, BNV, T, RES, RELU, G, S, F16, false, BMV>), grid, block, 0, st, \
-                       (const unsigned short*)x, (const unsigned short*)wp, gamma, beta, mean, var, eps,              \
-                       (const unsigned short*)res, y, (int)M, K, N, geo, stats, (const unsigned short*)res_gate)
 #define LG(BNV, T, BMV)                                                                 \
     if constexpr (PL == 1 && !OUTF32) {                                                 \
-        if (gate == 1) LK(BNV, T, true, false, 1, 0, BMV); else LK(BNV, T, true, false, 2, 0, BMV); \
+        if (gate == 1) LK(BNV, T, true, false, 1, 0, false, BMV); else LK(BNV, T, true, false, 2, 0, false, BMV); \
     }
 #define LS(BNV, T, BMV)                                                                 \
     if constexpr (PL == 1 && !OUTF32) {                                                 \
-        if (stats_mode == 2) LK(BNV, T, false, false, 0, 2, BMV);                       \
-        else LK(BNV, T, false, false, 0, 1, BMV);                                       \
+        if (c.stats_mode == 2) LK(BNV, T, false, false, 0, 2, false, BMV);              \
+        else LK(BNV, T, false, false, 0, 1, false, BMV);                                \
     }
 #define LL(BNV, T, BMV)                                                                 \
-    if (stats_mode == 2) { LS(BNV, T, BMV) }                                            \
-    else if (res) {                                                                     \
-        if (relu) LK(BNV, T, true, true, 0, 0, BMV);                                    \
-        else if (gate == 0) LK(BNV, T, true, false, 0, 0, BMV);                         \
+    if (c.stats_mode == 2) { LS(BNV, T, BMV) }                                          \
+    else if (c.res) {                                                                   \
+        if (c.relu) LK(BNV, T, true, true, 0, 0, false, BMV);                           \
+        else if (gate == 0) LK(BNV, T, true, false, 0, 0, false, BMV);                  \
         else { LG(BNV, T, BMV) }                                                        \
-    } else if (relu) LK(BNV, T, false, true, 0, 0, BMV);                                \
-    else if (!stats) LK(BNV, T, false, false, 0, 0, BMV);                               \
+    } else if (c.relu) LK(BNV, T, false, true, 0, 0, false, BMV);                       \
+    else if (c.stats_mode == 0) LK(BNV, T, false, false, 0, 0, false, BMV);             \
     else { LS(BNV, T, BMV) }
-    if (half9) {
-        if constexpr (!OUTF32 && PL == 2) LK(128, 9, false, true, 0, 0, 128);
-    } else if (half) {
+    if (r.half9) {
+        if constexpr (!OUTF32 && PL == 2) LK(128, 9, false, true, 0, 0, false, 128);
+    } else if (r.BM == 128) {
         if constexpr (!OUTF32) { LL(128, 1, 128) }
-    } else if (taps == 1) {
-        if (BN == 256) { LL(256, 1, 256) } else if (BN == 128) { LL(128, 1, 256) } else { LL(64, 1, 256) }
+    } else if (c.taps == 1) {
+        if (r.BN == 256) { LL(256, 1, 256) } else if (r.BN == 128) { LL(128, 1, 256) } else { LL(64, 1, 256) }
     } else {
-        if (BN == 256) { LL(256, 9, 256) } else if (BN == 128) { LL(128, 9, 256) } else { LL(64, 9, 256) }
+        if (r.BN == 256) { LL(256, 9, 256) } else if (r.BN == 128) { LL(128, 9, 256) } else { LL(64, 9, 256) }
     }
 #undef LL
 #undef LS

@@ -18,38 +18,26 @@
 #include <hip/hip_bf16.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv_launch.h"
 
 namespace hiast {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 xc_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float xc_f32x4;
-typedef __attribute__((address_space(3))) void* xc_lds_ptr;
 
 constexpr int XC_PANEL = 64;            // rows of X per panel
 constexpr int XC_STAGES = 3;
 constexpr int XC_COLS = 512;            // output columns per block (8 waves x 64)
 
-__device__ __forceinline__ void xc_dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds, int voff, int soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (xc_lds_ptr)lds, 16, voff, soff, 0, 0);
-}
-
-// same image as igemm.hip: 16-byte chunk c of row r of a [rows][128 B] slab tile lives at chunk c ^ ((r >> 1) & 7)
-__device__ __forceinline__ int xc_lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-
+// (LDS-DMA and the swizzled LDS image of a slab tile: h_dma16 / h_lds_off, common.h)
 // LDS fragment read as inline asm: the compiler orders every LDS load it knows about behind ALL pending LDS-DMA
 // (s_waitcnt vmcnt(0) in front of the first ds_read after a buffer_load ... lds — it cannot tell the stage being read
 // from the stage being filled), which would turn the two-panel prefetch into none.  The reads of one MFMA step are
 // issued together and waited for by xc_lds_wait (lgkmcnt), which also ties the registers so nothing is moved across it.
-__device__ __forceinline__ xc_bf16x8 xc_lds_read(unsigned addr)
+__device__ __forceinline__ h_bf16x8 xc_lds_read(unsigned addr)
 {
-    xc_bf16x8 v;
+    h_bf16x8 v;
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
     return v;
 }
-__device__ __forceinline__ void xc_lds_wait(xc_bf16x8& a, xc_bf16x8& b)
+__device__ __forceinline__ void xc_lds_wait(h_bf16x8& a, h_bf16x8& b)
 {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b));
 }
@@ -95,12 +83,12 @@ __global__ __launch_bounds__(512) void xconv_kernel(const unsigned short* __rest
 
     // ---- weights -> registers, in the A-operand layout of v_mfma_f32_16x16x32_bf16 (lane: row px, k = 8 g .. 8 g + 7
     // of a 32-deep step); row px of n-tile b is output channel n0 + xc_chan(px >> 2, b, px & 3)
-    xc_bf16x8 wr[4][KS];
+    h_bf16x8 wr[4][KS];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         const unsigned short* wrow = Wp + (size_t)(n0 + xc_chan(px >> 2, b, px & 3)) * KC + g * 8;
 #pragma unroll
-        for (int s = 0; s < KS; ++s) wr[b][s] = *reinterpret_cast<const xc_bf16x8*>(wrow + s * 32);
+        for (int s = 0; s < KS; ++s) wr[b][s] = *reinterpret_cast<const h_bf16x8*>(wrow + s * 32);
     }
     // pin the fragments down HERE: with their first use inside the panel loop the compiler's wait for these loads
     // lands in the loop as an s_waitcnt vmcnt(0) behind every DMA issue (measured: the prefetch was dead)
@@ -129,7 +117,7 @@ __global__ __launch_bounds__(512) void xconv_kernel(const unsigned short* __rest
         const int voff = (p < npanel && m < M) ? (int)((size_t)m * KC * 2) + dchunk : OOB;
         unsigned char* base = smem + st * STAGE + wave * 1024;
 #pragma unroll
-        for (int j = 0; j < SL; ++j) xc_dma16(xrs, base + j * (XC_PANEL * 128), voff, j * 128);
+        for (int j = 0; j < SL; ++j) h_dma16(xrs, base + j * (XC_PANEL * 128), voff, j * 128);
     };
 
     const unsigned lds_base = (unsigned)(size_t)smem;       // LDS byte address of the stage buffers (for the asm reads)
@@ -178,20 +166,20 @@ __global__ __launch_bounds__(512) void xconv_kernel(const unsigned short* __rest
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             if (RES && half == 1) load_res(1);
-            xc_f32x4 acc[2][4];
+            h_f32x4 acc[2][4];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 4; ++b) acc[a][b] = (xc_f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int b = 0; b < 4; ++b) acc[a][b] = (h_f32x4){0.f, 0.f, 0.f, 0.f};
             // fragments of step s + 1 are requested before the MFMAs of step s (LDS latency hidden behind 8 MFMAs)
             auto frag = [&](int s, int a) {
                 return xc_lds_read(lds_base + (unsigned)(st * STAGE + (s >> 1) * (XC_PANEL * 128) +
-                                                         xc_lds_off(half * 32 + a * 16 + px, (s & 1) * 4 + g)));
+                                                         h_lds_off(half * 32 + a * 16 + px, (s & 1) * 4 + g)));
             };
             // (double-buffered where the registers allow it: the statistics accumulators / BN + residual temporaries
             // of those variants would otherwise spill, and scratch traffic would break the vmcnt bookkeeping above)
             constexpr bool DB = !(STATS || (BN && RES));
-            xc_bf16x8 xa[DB ? 2 : 1][2];
+            h_bf16x8 xa[DB ? 2 : 1][2];
             xa[0][0] = frag(0, 0);
             xa[0][1] = frag(0, 1);
             xc_lds_wait(xa[0][0], xa[0][1]);
@@ -322,69 +310,53 @@ __global__ __launch_bounds__(512) void xconv_kernel(const unsigned short* __rest
     }
 }
 
-static int xc_blocks(int64_t M, int N)
-{
-    const int NG = N / XC_COLS;
-    const long long npanel = (M + XC_PANEL - 1) / XC_PANEL;
-    static const int env_cus = [] { const char* e = getenv("HIAST_XCONV_CUS"); const int v = e ? atoi(e) : 0; return v >= 8 && v <= 256 ? v : 0; }();
-    const int cus = env_cus ? env_cus : hiast_grid_cus();   // one block per CU (HIAST_XCONV_CUS: experiment, part of the chip)
-    long long streams = cus / NG / 8 * 8;           // the (slot, xcd) numbering wants whole rounds of the 8 XCDs
-    if (streams < 8) streams = 8;
-    if (streams > npanel) streams = (npanel + 7) / 8 * 8;
-    return (int)(streams * NG);
-}
-
 }  // namespace hiast
 
-// shapes this kernel takes over from the tile kernel (plain bf16, 1x1)
-int hiast_xconv_ok(int64_t M, int K, int N, int planes, int taps, int out_f32, int has_bn, int has_res, int relu,
-                   int has_gate, int gate_mask, int has_stats)
+// shapes this kernel takes over from the tile kernel (plain bf16 / fp16, 1x1)
+int hiast_xconv_ok(const ConvLaunch& c)
 {
     const char* env = getenv("HIAST_XCONV");          // HIAST_XCONV=0: A/B switch back to the tile kernel
-    if ((env && atoi(env) == 0) || planes != 1 || taps != 1 || out_f32) return 0;
-    if (K != 256 || N % hiast::XC_COLS != 0 || N > 2048) return 0;
-    if (has_gate && (!gate_mask || !has_res || relu)) return 0;
-    if (has_bn && has_res && !relu) return 0;        // (no caller in the trunk; that variant would need scratch)
-    if (has_stats && (has_res || relu || has_bn)) return 0;      // the statistics variant is the plain GEMM only
-    if (M < 4096) return 0;                          // small maps: the tile kernel's grid fills the chip better
+    const bool has_bn = c.mean != nullptr, has_res = c.res != nullptr;
+    if ((env && atoi(env) == 0) || c.planes() != 1 || c.taps != 1 || c.out_f32) return 0;
+    if (c.K != 256 || c.N % hiast::XC_COLS != 0 || c.N > 2048) return 0;
+    if (c.res_gate && (!c.gate_mask || !has_res || c.relu)) return 0;
+    if (has_bn && has_res && !c.relu) return 0;      // (no caller in the trunk; that variant would need scratch)
+    if (c.stats_mode == 1 && (has_res || c.relu || has_bn)) return 0;      // the statistics variant is the plain GEMM only
+    if (c.M < 4096) return 0;                        // small maps: the tile kernel's grid fills the chip better
     return 1;
 }
 
 int hiast_xconv_stats_rows(int64_t M, int N)
 {
-    return hiast::xc_blocks(M, N) / (N / hiast::XC_COLS);
+    return conv_panel_streams(M, N / hiast::XC_COLS, hiast::XC_PANEL);
 }
 
-int hiast_xconv_launch(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                       const float* var, float eps, const void* res, int relu, void* y, int64_t M, int K, int N,
-                       float* stats, const void* res_gate, int f16, hipStream_t st)
+int hiast_xconv_launch(const ConvLaunch& c, const ConvRoute& r)
 {
     using namespace hiast;
-    const dim3 grid((unsigned)xc_blocks(M, N));
+    const dim3 grid((unsigned)(r.rows * (c.N / XC_COLS)));      // the route's panel streams x column groups
+#define XK(BNF, RESF, RELUF, GATEF, STATSF, F16)                                                                      \
+    hipLaunchKernelGGL((xconv_kernel<256, BNF, RESF, RELUF, GATEF, STATSF, F16>), grid, dim3(512), 0, c.st,           \
+                       (const unsigned short*)c.x, (const unsigned short*)c.wp, c.gamma, c.beta, c.mean, c.var, c.eps, \
+                       (const unsigned short*)c.res, (const unsigned char*)c.res_gate, (unsigned short*)c.y, (int)c.M, c.N, \
+                       c.stats)
 #define XL(BNF, RESF, RELUF, GATEF, STATSF)                                                                          \
     do {                                                                                                             \
-        if (f16)                                                                                                     \
-            hipLaunchKernelGGL((xconv_kernel<256, BNF, RESF, RELUF, GATEF, STATSF, true>), grid, dim3(512), 0, st,    \
-                               (const unsigned short*)x, (const unsigned short*)wp, gamma, beta, mean, var, eps,      \
-                               (const unsigned short*)res, (const unsigned char*)res_gate, (unsigned short*)y, (int)M, N, \
-                               stats);                                                                               \
-        else                                                                                                         \
-            hipLaunchKernelGGL((xconv_kernel<256, BNF, RESF, RELUF, GATEF, STATSF>), grid, dim3(512), 0, st,          \
-                               (const unsigned short*)x, (const unsigned short*)wp, gamma, beta, mean, var, eps,      \
-                               (const unsigned short*)res, (const unsigned char*)res_gate, (unsigned short*)y, (int)M, N, \
-                               stats);                                                                               \
+        if (c.f16()) XK(BNF, RESF, RELUF, GATEF, STATSF, true);                                                      \
+        else XK(BNF, RESF, RELUF, GATEF, STATSF, false);                                                             \
     } while (0)
-    const bool bn = mean != nullptr;
-    if (stats) { XL(false, false, false, false, true); }
-    else if (res_gate) { XL(false, true, false, true, false); }
-    else if (res) {
-        if (bn) { if (relu) XL(true, true, true, false, false); else return HIAST_E_RANGE; }
-        else { if (relu) XL(false, true, true, false, false); else XL(false, true, false, false, false); }
+    const bool bn = c.mean != nullptr;
+    if (c.stats) { XL(false, false, false, false, true); }
+    else if (c.res_gate) { XL(false, true, false, true, false); }
+    else if (c.res) {
+        if (bn) { if (c.relu) XL(true, true, true, false, false); else return HIAST_E_RANGE; }
+        else { if (c.relu) XL(false, true, true, false, false); else XL(false, true, false, false, false); }
     } else {
-        if (bn) { if (relu) XL(true, false, true, false, false); else XL(true, false, false, false, false); }
-        else { if (relu) XL(false, false, true, false, false); else XL(false, false, false, false, false); }
+        if (bn) { if (c.relu) XL(true, false, true, false, false); else XL(true, false, false, false, false); }
+        else { if (c.relu) XL(false, false, true, false, false); else XL(false, false, false, false, false); }
     }
 #undef XL
+#undef XK
     HIAST_CHECK_LAUNCH();
     return 0;
 }

@@ -21,12 +21,9 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "conv_launch.h"
 
 namespace hiast {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 x2_bf16x8;
-typedef __attribute__((address_space(3))) void* x2_lds_ptr;
 
 constexpr int X2_PANEL = 32;            // rows of X per panel
 constexpr int X2_STAGES = 3;
@@ -35,24 +32,17 @@ constexpr int X2_K = 256;               // reduction length (channels)
 constexpr int X2_ROWB = X2_K * 4;       // bytes per activation row (hi | lo planes)
 constexpr int X2_STAGE = X2_PANEL * X2_ROWB;      // 32 KiB
 
-__device__ __forceinline__ void x2_dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds, int voff, int soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (x2_lds_ptr)lds, 16, voff, soff, 0, 0);
-}
-
-// LDS image of one slab tile [rows][128 B]: 16-byte chunk c of row r lives at chunk c ^ ((r >> 1) & 7) (as igemm / xconv)
-__device__ __forceinline__ int x2_lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
+// (LDS-DMA and the swizzled LDS image of a slab tile: h_dma16 / h_lds_off, common.h)
 // fragment reads as inline asm + explicit lgkmcnt wait (the compiler orders every LDS load it can see behind ALL pending
 // LDS-DMA: s_waitcnt vmcnt(0), which would serialise the two-panel prefetch)
 template <int OFF>
-__device__ __forceinline__ x2_bf16x8 x2_lds_read(unsigned addr)
+__device__ __forceinline__ h_bf16x8 x2_lds_read(unsigned addr)
 {
-    x2_bf16x8 v;
+    h_bf16x8 v;
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
     return v;
 }
-__device__ __forceinline__ void x2_lds_wait(x2_bf16x8& a, x2_bf16x8& b, x2_bf16x8& c, x2_bf16x8& d)
+__device__ __forceinline__ void x2_lds_wait(h_bf16x8& a, h_bf16x8& b, h_bf16x8& c, h_bf16x8& d)
 {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 }
@@ -94,14 +84,14 @@ __global__ __launch_bounds__(512) void xconv2_kernel(const unsigned short* __res
     // 32-deep step).  Row px of n-tile b (b = 0, 1) is output channel n0 + (px >> 2) * 8 + b * 4 + (px & 3): lane group g
     // of a pixel then holds channels g * 8 .. g * 8 + 7 (tile 0: + 0..3, tile 1: + 4..7) — one 16-byte piece of the slab.
     // Packed weight row (hiast_pack_conv_weight, split planes): [slab s][32 hi | 32 lo].
-    x2_bf16x8 wh[2][KS], wl[2][KS];
+    h_bf16x8 wh[2][KS], wl[2][KS];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const unsigned short* wrow = Wp + (size_t)(n0 + (px >> 2) * 8 + b * 4 + (px & 3)) * (2 * X2_K) + g * 8;
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            wh[b][s] = *reinterpret_cast<const x2_bf16x8*>(wrow + s * 64);
-            wl[b][s] = *reinterpret_cast<const x2_bf16x8*>(wrow + s * 64 + 32);
+            wh[b][s] = *reinterpret_cast<const h_bf16x8*>(wrow + s * 64);
+            wl[b][s] = *reinterpret_cast<const h_bf16x8*>(wrow + s * 64 + 32);
         }
     }
     // pin the fragments down HERE (first use inside the panel loop would put the compiler's wait for these loads — an
@@ -129,7 +119,7 @@ __global__ __launch_bounds__(512) void xconv2_kernel(const unsigned short* __res
         const int voff = (p < npanel && m < M) ? (int)((size_t)m * X2_ROWB) + dchunk : OOB;
         unsigned char* base = smem + st * X2_STAGE + rgrp * 1024;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) x2_dma16(xrs, base + (j0 + j) * (X2_PANEL * 128), voff, (j0 + j) * 128);
+        for (int j = 0; j < 4; ++j) h_dma16(xrs, base + (j0 + j) * (X2_PANEL * 128), voff, (j0 + j) * 128);
     };
     const unsigned lds_base = (unsigned)(size_t)smem;
 
@@ -194,10 +184,10 @@ __global__ __launch_bounds__(512) void xconv2_kernel(const unsigned short* __res
         // < 50 % busy; while one wave of a SIMD waits ~100 cycles for its four reads the other one issues MFMAs.
         // Addresses: everything but the swizzled chunk is an instruction immediate — step s = + s * 4 KiB, row tile 1 =
         // + 2 KiB (16 rows: the swizzle (row >> 1) & 7 is the same for px and px + 16), lo plane = chunk + 4 = address XOR 64.
-        const unsigned fa = lds_base + (unsigned)(st * X2_STAGE + x2_lds_off(px, g));
+        const unsigned fa = lds_base + (unsigned)(st * X2_STAGE + h_lds_off(px, g));
         const unsigned fb = fa ^ 64u;
         // ring of two fragment sets: the reads of step S + 1 are in flight under the 12 MFMAs of step S
-        x2_bf16x8 xh[2][2], xl[2][2];                    // [ring][row tile]
+        h_bf16x8 xh[2][2], xl[2][2];                    // [ring][row tile]
 #define X2_READ(S, R)                                                                                               \
         xh[R][0] = x2_lds_read<(S) * 4096>(fa);        xl[R][0] = x2_lds_read<(S) * 4096>(fb);                      \
         xh[R][1] = x2_lds_read<(S) * 4096 + 2048>(fa); xl[R][1] = x2_lds_read<(S) * 4096 + 2048>(fb);
@@ -280,43 +270,30 @@ __global__ __launch_bounds__(512) void xconv2_kernel(const unsigned short* __res
 #endif
 }
 
-static int x2_blocks(int64_t M, int N)
-{
-    const int NG = N / X2_COLS;
-    const long long npanel = (M + X2_PANEL - 1) / X2_PANEL;
-    static const int env_cus = [] { const char* e = getenv("HIAST_XCONV_CUS"); const int v = e ? atoi(e) : 0; return v >= 8 && v <= 256 ? v : 0; }();
-    const int cus = env_cus ? env_cus : hiast_grid_cus();   // one block per CU (HIAST_XCONV_CUS: experiment, part of the chip)
-    long long streams = cus / NG / 8 * 8;           // the (slot, xcd) numbering wants whole rounds of the 8 XCDs
-    if (streams < 8) streams = 8;
-    if (streams > npanel) streams = (npanel + 7) / 8 * 8;
-    return (int)(streams * NG);
-}
-
 }  // namespace hiast
 
 // shapes this kernel takes over from the tile kernel: split planes, 1x1, K = 256, BatchNorm(eval) in the epilogue
-int hiast_xconv2_ok(int64_t M, int K, int N, int planes, int taps, int out_f32, int has_bn, int has_res, int relu,
-                    int has_gate, int has_stats)
+int hiast_xconv2_ok(const ConvLaunch& c)
 {
     const char* env = getenv("HIAST_XCONV2");        // HIAST_XCONV2=0: A/B switch back to the tile kernel
-    if ((env && atoi(env) == 0) || planes != 2 || taps != 1 || out_f32 || has_gate || has_stats) return 0;
-    if (K != hiast::X2_K || N % hiast::X2_COLS != 0 || N > 2048 || !has_bn) return 0;
-    if (has_res && !relu) return 0;                  // (no caller in the trunk)
-    if (M < 4096) return 0;                          // small maps: the tile kernel's grid fills the chip better
+    if ((env && atoi(env) == 0) || c.planes() != 2 || c.taps != 1 || c.out_f32 || c.res_gate || c.stats_mode != 0) return 0;
+    if (c.K != hiast::X2_K || c.N % hiast::X2_COLS != 0 || c.N > 2048 || !c.mean) return 0;
+    if (c.res && !c.relu) return 0;                  // (no caller in the trunk)
+    if (c.M < 4096) return 0;                        // small maps: the tile kernel's grid fills the chip better
     return 1;
 }
 
-int hiast_xconv2_launch(const void* x, const void* wp, const float* gamma, const float* beta, const float* mean,
-                        const float* var, float eps, const void* res, int relu, void* y, int64_t M, int N, hipStream_t st)
+int hiast_xconv2_launch(const ConvLaunch& c)
 {
     using namespace hiast;
-    const dim3 grid((unsigned)x2_blocks(M, N));
+    const int NG = c.N / X2_COLS;
+    const dim3 grid((unsigned)(conv_panel_streams(c.M, NG, X2_PANEL) * NG));
 #define X2L(RESF, RELUF)                                                                                          \
-    hipLaunchKernelGGL((xconv2_kernel<RESF, RELUF>), grid, dim3(512), 0, st, (const unsigned short*)x,             \
-                       (const unsigned short*)wp, gamma, beta, mean, var, eps, (const unsigned short*)res,         \
-                       (unsigned short*)y, (int)M, N)
-    if (res) X2L(true, true);
-    else if (relu) X2L(false, true);
+    hipLaunchKernelGGL((xconv2_kernel<RESF, RELUF>), grid, dim3(512), 0, c.st, (const unsigned short*)c.x,         \
+                       (const unsigned short*)c.wp, c.gamma, c.beta, c.mean, c.var, c.eps, (const unsigned short*)c.res, \
+                       (unsigned short*)c.y, (int)c.M, c.N)
+    if (c.res) X2L(true, true);
+    else if (c.relu) X2L(false, true);
     else X2L(false, false);
 #undef X2L
     HIAST_CHECK_LAUNCH();

@@ -22,31 +22,22 @@
 
 namespace hiast {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 xb_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float xb_f32x4;
-typedef __attribute__((address_space(3))) void* xb_lds_ptr;
-
 constexpr int XB_PANEL = 64;            // rows of X per panel
 constexpr int XB_STAGES = 3;
 constexpr int XB_COLS = 256;            // output columns per block (8 waves x 32)
 constexpr int XB_KC = 256;              // reduction length (conv1's output channels)
 
-__device__ __forceinline__ void xb_dma16(__amdgpu_buffer_rsrc_t rs, unsigned char* lds, int voff, int soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (xb_lds_ptr)lds, 16, voff, soff, 0, 0);
-}
-// same LDS image as igemm.hip / xconv.hip: 16-byte chunk c of row r of a [rows][128 B] slab tile lives at chunk c ^ ((r >> 1) & 7)
-__device__ __forceinline__ int xb_lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
+// (LDS-DMA and the swizzled LDS image of a slab tile: h_dma16 / h_lds_off, common.h)
 // fragment read with the tile offset as the instruction's immediate (idx * 2 KiB): two base registers per panel serve all 32
 // reads of a half (computed per read, the addresses were 32 more live VGPRs and the kernel spilled)
 template <int IDX>
-__device__ __forceinline__ xb_bf16x8 xb_lds_read_i(unsigned addr)
+__device__ __forceinline__ h_bf16x8 xb_lds_read_i(unsigned addr)
 {
-    xb_bf16x8 v;
+    h_bf16x8 v;
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(IDX * 2048));
     return v;
 }
-__device__ __forceinline__ xb_bf16x8 xb_lds_read(unsigned addr, int idx)     // idx is a constant after unrolling
+__device__ __forceinline__ h_bf16x8 xb_lds_read(unsigned addr, int idx)     // idx is a constant after unrolling
 {
     switch (idx) {
     case 1: return xb_lds_read_i<1>(addr);
@@ -67,7 +58,7 @@ __device__ __forceinline__ xb_bf16x8 xb_lds_read(unsigned addr, int idx)     // 
     default: return xb_lds_read_i<0>(addr);
     }
 }
-__device__ __forceinline__ void xb_lds_wait(xb_bf16x8& a, xb_bf16x8& b)
+__device__ __forceinline__ void xb_lds_wait(h_bf16x8& a, h_bf16x8& b)
 {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b));
 }
@@ -99,12 +90,12 @@ __global__ __launch_bounds__(512) void xconv_gated_bnstat_kernel(
 
     // weights -> registers in the A-operand layout of v_mfma_f32_16x16x32 (lane: row px, k = 8 g .. 8 g + 7 of a step); row px of
     // n-tile b (0 | 1) is output channel n0 + (px >> 2) * 8 + b * 4 + (px & 3): lane group g' of D then holds channels 8 g' + 4 b + r
-    xb_bf16x8 wr[2][KS];
+    h_bf16x8 wr[2][KS];
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const unsigned short* wrow = Wp + (size_t)(n0 + (px >> 2) * 8 + b * 4 + (px & 3)) * XB_KC + g * 8;
 #pragma unroll
-        for (int s = 0; s < KS; ++s) wr[b][s] = *reinterpret_cast<const xb_bf16x8*>(wrow + s * 32);
+        for (int s = 0; s < KS; ++s) wr[b][s] = *reinterpret_cast<const h_bf16x8*>(wrow + s * 32);
     }
     // pin the weights down HERE (xconv.hip: with the first use inside the panel loop the compiler's wait for these loads lands in
     // the loop as an s_waitcnt vmcnt(0) behind every DMA issue)
@@ -123,7 +114,7 @@ __global__ __launch_bounds__(512) void xconv_gated_bnstat_kernel(
         const int voff = (p < npanel && m < M) ? (int)((size_t)m * XB_KC * 2) + dchunk : OOB;
         unsigned char* base = smem + st * STAGE + wave * 1024;
 #pragma unroll
-        for (int j = 0; j < SL; ++j) xb_dma16(xrs, base + j * (XB_PANEL * 128), voff, j * 128);
+        for (int j = 0; j < SL; ++j) h_dma16(xrs, base + j * (XB_PANEL * 128), voff, j * 128);
     };
     const unsigned lds_base = (unsigned)(size_t)smem;
     // Σg and Σ g*x per channel (RAW x: the BatchNorm's mean / invstd are applied once, at the end — Σ g*xhat = invstd * (Σ g*x -
@@ -163,20 +154,20 @@ __global__ __launch_bounds__(512) void xconv_gated_bnstat_kernel(
         else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(SL + 4) : "memory");
         load_rows(nxt, p + nstream);
         issue(p + 2 * nstream, (it + 2) % XB_STAGES);
-        const unsigned fbase = lds_base + (unsigned)(st * STAGE) + (unsigned)xb_lds_off(px, g);
+        const unsigned fbase = lds_base + (unsigned)(st * STAGE) + (unsigned)h_lds_off(px, g);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            xb_f32x4 acc[2][2];
+            h_f32x4 acc[2][2];
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int b = 0; b < 2; ++b) acc[a][b] = (xb_f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int b = 0; b < 2; ++b) acc[a][b] = (h_f32x4){0.f, 0.f, 0.f, 0.f};
             // row = 32 half + 16 a + px: its swizzle ((row >> 1) & 7) depends on px only, and the two 32-deep halves of a slab
             // are chunks g and g ^ 4: address = fbase ^ (64 if s odd) + 2 KiB * (4 (s >> 1) + 2 half + a)
             auto frag = [&](int s, int a) {
                 return xb_lds_read((s & 1) ? fbase ^ 64u : fbase, 4 * (s >> 1) + 2 * half + a);
             };
-            xb_bf16x8 xa[2][2];
+            h_bf16x8 xa[2][2];
             xa[0][0] = frag(0, 0);
             xa[0][1] = frag(0, 1);
             xb_lds_wait(xa[0][0], xa[0][1]);

@@ -42,7 +42,7 @@ constexpr int BB_BM = 256;       // pixels per block (8 waves x 32)
 // the channels 8 g .. 8 g + 3 and 8 g + 4 .. 8 g + 7 of a pixel
 __host__ __device__ __forceinline__ int bb_chan(int q) { return (q & ~31) + (((q & 15) >> 2) << 3) + (((q >> 4) & 1) << 2) + (q & 3); }
 
-__device__ __forceinline__ void bb_read_tile(ig_bf16x8 (&f)[2], unsigned addr, int ct)       // ct is a constant after unrolling
+__device__ __forceinline__ void bb_read_tile(h_bf16x8 (&f)[2], unsigned addr, int ct)       // ct is a constant after unrolling
 {
 #define BB_C(I) case I: f[0] = ig_lds_read<(I) * 2048>(addr); f[1] = ig_lds_read<(I) * 2048>(addr ^ 64u); break;
     switch (ct) {
@@ -55,9 +55,9 @@ __device__ __forceinline__ void bb_read_tile(ig_bf16x8 (&f)[2], unsigned addr, i
 // BatchNorm tables live in the operand buffer: read them with inline asm like the fragments (a C++ LDS load would make the
 // compiler drain every pending LDS-DMA first)
 template <int OFF>
-__device__ __forceinline__ ig_f32x4 bb_lds_f4(unsigned addr)
+__device__ __forceinline__ h_f32x4 bb_lds_f4(unsigned addr)
 {
-    ig_f32x4 v;
+    h_f32x4 v;
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
     return v;
 }
@@ -160,18 +160,18 @@ __global__ __launch_bounds__(512) void b2b_kernel(
         const int yy = ay[g] + (tap / 3 - 1) * geo.dil, xx = ax[g] + (tap % 3 - 1) * geo.dil;
         const bool ok = aok[g] & on & ((unsigned)yy < (unsigned)geo.H) & ((unsigned)xx < (unsigned)geo.W);
         const int pix = (an[g] * geo.H + yy) * geo.W + xx;
-        ig_dma16(xrs, smem + sa * A_BYTES + (4 * wave + g) * 1024, ok ? pix * (KS * 128) + achunk[g] : OOB, j * 128);
+        h_dma16(xrs, smem + sa * A_BYTES + (4 * wave + g) * 1024, ok ? pix * (KS * 128) + achunk[g] : OOB, j * 128);
     };
     auto dma_b = [&](int kt, int sb, int g, bool on) {
         const int j = kt / 9, tap = kt - j * 9;
-        ig_dma16(wrs, smem + NSA * A_BYTES + sb * B_BYTES + (4 * wave + g) * 1024, on ? bvoff[g] : OOB, (tap * KS + j) * 128);
+        h_dma16(wrs, smem + NSA * A_BYTES + sb * B_BYTES + (4 * wave + g) * 1024, on ? bvoff[g] : OOB, (tap * KS + j) * 128);
     };
 
-    ig_f32x4 acc[16][2];                                 // [16-channel tile][16-pixel tile]
+    h_f32x4 acc[16][2];                                 // [16-channel tile][16-pixel tile]
 #pragma unroll
     for (int c = 0; c < 16; ++c)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) acc[c][p] = (ig_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int p = 0; p < 2; ++p) acc[c][p] = (h_f32x4){0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
     for (int g = 0; g < 4; ++g) dma_a(0, 0, g, true);
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(512) void b2b_kernel(
         sa = sa == 2 ? 0 : sa + 1;
         // pixel fragments of the whole k-step stay in registers (16); weight fragments go through a ring of three 16-channel
         // tiles: tile c + 2 is requested behind the MFMAs of tile c
-        ig_bf16x8 xf[2][2], wf[3][2];
+        h_bf16x8 xf[2][2], wf[3][2];
         xf[0][0] = ig_lds_read<0>(ca);    xf[0][1] = ig_lds_read<0>(ca ^ 64u);
         xf[1][0] = ig_lds_read<2048>(ca); xf[1][1] = ig_lds_read<2048>(ca ^ 64u);
         bb_read_tile(wf[0], cb, 0);
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(512) void b2b_kernel(
         const int voff = t < NT ? w3voff : OOB;
         unsigned char* base = smem + st * W3_STAGE + rgrp * 1024;
 #pragma unroll
-        for (int j = 0; j < DW; ++j) ig_dma16(w3rs, base + (j0 + j) * 4096, voff, t * (32 * KS * 128) + (j0 + j) * 128);
+        for (int j = 0; j < DW; ++j) h_dma16(w3rs, base + (j0 + j) * 4096, voff, t * (32 * KS * 128) + (j0 + j) * 128);
     };
     // identity rows / output rows of this lane: pixel m0 + 32 wave + 16 p + r16, channels 32 t + 8 kq .. + 7
     // (split planes: hi at the slab's byte 16 kq, lo at + 64; one plane: byte 64 t + 16 kq of the row)
@@ -336,12 +336,12 @@ __global__ __launch_bounds__(512) void b2b_kernel(
     load_res(0, 0);
 
     // a2 = relu(bn2(acc)) as the B-operand fragments of the 1x1: k-step s (channels 32 s .. + 31), pixel tile p
-    ig_bf16x8 ah[8][2], al[PL == 2 ? 8 : 1][2];
+    h_bf16x8 ah[8][2], al[PL == 2 ? 8 : 1][2];
     const unsigned t2 = lds_base + (unsigned)(OFF_BN2 + kq * 32);
 #define BB_CONV(S)                                                                                                         \
     {                                                                                                                      \
-        ig_f32x4 c0 = bb_lds_f4<(S) * 128>(t2), c1 = bb_lds_f4<(S) * 128 + 16>(t2);                                        \
-        ig_f32x4 d0 = bb_lds_f4<1024 + (S) * 128>(t2), d1 = bb_lds_f4<1024 + (S) * 128 + 16>(t2);                          \
+        h_f32x4 c0 = bb_lds_f4<(S) * 128>(t2), c1 = bb_lds_f4<(S) * 128 + 16>(t2);                                        \
+        h_f32x4 d0 = bb_lds_f4<1024 + (S) * 128>(t2), d1 = bb_lds_f4<1024 + (S) * 128 + 16>(t2);                          \
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(c0), "+v"(c1), "+v"(d0), "+v"(d1));                                     \
         _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                                    \
             float v[8];                                                                                                    \
@@ -363,8 +363,8 @@ __global__ __launch_bounds__(512) void b2b_kernel(
                 ph[q] = (unsigned)h0 | ((unsigned)h1 << 16);                                                               \
                 pl_[q] = (unsigned)l0 | ((unsigned)l1 << 16);                                                              \
             }                                                                                                              \
-            ah[S][p] = __builtin_bit_cast(ig_bf16x8, (bb_u32x4){ph[0], ph[1], ph[2], ph[3]});                              \
-            if (PL == 2) al[S][p] = __builtin_bit_cast(ig_bf16x8, (bb_u32x4){pl_[0], pl_[1], pl_[2], pl_[3]});            \
+            ah[S][p] = __builtin_bit_cast(h_bf16x8, (bb_u32x4){ph[0], ph[1], ph[2], ph[3]});                              \
+            if (PL == 2) al[S][p] = __builtin_bit_cast(h_bf16x8, (bb_u32x4){pl_[0], pl_[1], pl_[2], pl_[3]});            \
         }                                                                                                                  \
         /* pin the results between the volatile table reads (else all 32 reads are issued first: 128 live registers) */    \
         asm volatile("" : "+v"(ah[S][0]), "+v"(ah[S][1]));                                                                 \
@@ -394,13 +394,13 @@ __global__ __launch_bounds__(512) void b2b_kernel(
         issue_w3(t + 2, (t + 2) % NS3);
         __builtin_amdgcn_sched_barrier(0);
 
-        ig_f32x4 o4[2][2];                               // [pixel tile][channel tile b]
+        h_f32x4 o4[2][2];                               // [pixel tile][channel tile b]
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int b = 0; b < 2; ++b) o4[p][b] = (ig_f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int b = 0; b < 2; ++b) o4[p][b] = (h_f32x4){0.f, 0.f, 0.f, 0.f};
         const unsigned fa = f3 + (unsigned)(st * W3_STAGE);
-        ig_bf16x8 wh[2][2], wl[2][2];                    // [ring][b]
+        h_bf16x8 wh[2][2], wl[2][2];                    // [ring][b]
 #define BB_READ(S, RG)                                                                                                     \
         if (PL == 2) {                                                                                                     \
             wh[RG][0] = ig_lds_read<(S) * 4096>(fa);        wl[RG][0] = ig_lds_read<(S) * 4096>(fa ^ 64u);                 \
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(512) void b2b_kernel(
         float sc[8], sh[8];
         {
             const unsigned ta = t3 + (unsigned)(t * 128);
-            ig_f32x4 s0 = bb_lds_f4<0>(ta), s1 = bb_lds_f4<16>(ta), t0 = bb_lds_f4<4096>(ta), t1 = bb_lds_f4<4096 + 16>(ta);
+            h_f32x4 s0 = bb_lds_f4<0>(ta), s1 = bb_lds_f4<16>(ta), t0 = bb_lds_f4<4096>(ta), t1 = bb_lds_f4<4096 + 16>(ta);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(s0), "+v"(s1), "+v"(t0), "+v"(t1));
 #pragma unroll
             for (int r = 0; r < 4; ++r) { sc[r] = s0[r]; sc[4 + r] = s1[r]; sh[r] = t0[r]; sh[4 + r] = t1[r]; }
