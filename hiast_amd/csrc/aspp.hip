@@ -723,6 +723,11 @@ extern "C" int hiast_aspp_fwd(const float* x, const float* wpack, float* y, int 
     const hiast::Taps taps = hiast::make_taps(dil);
     hipStream_t st = (hipStream_t)stream;
     const bool narrow = Cout <= 19;                 // 16 MFMA rows + up to 3 VALU channels
+    // aspp_fwd16_kernel addresses an image through a buffer descriptor: num_records = Cin*hw*4 bytes as a 32-bit value, signed
+    // 32-bit byte offsets (sbase = cib*hw*4), and 0x80000000 as the offset that must lie outside the image for the zero
+    // padding.  All three hold only while one image has at most 2^31 bytes.  (The 32-row kernel, bwd_data and bwd_weight form
+    // their addresses as size_t element offsets from ints below hw: aspp_check's 2^31 elements covers them.)
+    if (narrow && (long long)Cin * hw * (long long)sizeof(float) > (1ll << 31)) return HIAST_E_RANGE;
     constexpr int MT = 2, NP = 4;
     const int px_per_block = narrow ? 4 * 16 * NP : 128 * MT;
     const int splitk = hiast::pick_splitk(B, hw, Cin, px_per_block);

@@ -203,7 +203,9 @@ int hiast_st_loss_cst_bwd(const float* logits_lr, const float* teacher_lr, const
  * wpack: hiast_aspp_wpack_bytes() scratch written by hiast_aspp_pack_weights (repacked
  * [33][Cin][32] weights + summed bias) and read by fwd / bwd_data; dil: host int[4].
  * workspace: hiast_aspp_workspace_bytes() scratch (split-K partial sums, fixed-order reduce:
- * results are bitwise reproducible; no float atomics). */
+ * results are bitwise reproducible; no float atomics).
+ * One image (Cin*h*w values) must stay below 2^31 elements; the forward with Cout <= 19 addresses it with 32-bit BYTE
+ * offsets and refuses an image above 2^31 bytes (HIAST_E_RANGE, before the workspace is looked at). */
 size_t hiast_aspp_wpack_bytes(int Cin, int Cout);
 size_t hiast_aspp_workspace_bytes(int B, int Cin, int h, int w, int Cout);
 int hiast_aspp_pack_weights(const float* w0, const float* w1, const float* w2, const float* w3,
