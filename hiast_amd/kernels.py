@@ -269,6 +269,61 @@ def tta_fused(zs, zfs, sizes, H, W, want_probs=False, want_label=True):
     return probs, label
 
 
+_pass1_tta_ws = {}
+
+
+def plabel_pass1_tta_supported(C, n_scales):
+    """whether hiast_plabel_pass1_tta covers this class count / number of scales (it returns HIAST_E_RANGE otherwise)"""
+    return int(C) in TTA_FUSED_CLASSES and 1 <= int(n_scales) <= TTA_FUSED_MAX_SCALES
+
+
+def plabel_pass1_tta(zs, zfs, sizes, H, W, hist=None):
+    """pass 1 over several views (hiast_plabel_pass1_tta): zs / zfs lists of fp32 [B,C,hs,ws] low-res head outputs of the
+    resized images / their mirror images (zfs None = no flip), sizes list of (Hs, Ws) the image was resized to
+    -> (maxprob f32 [B,H,W] = mean probability of the label over the views, argmax u8 [B,H,W] = the validator's label,
+    hist u32-as-int32 [C,NBINS] (accumulated))"""
+    n = len(zs)
+    assert n == len(sizes) and n > 0
+    B, C = zs[0].shape[:2]
+    for z in zs:
+        _req(z, torch.float32, 4, "z")
+        assert tuple(z.shape[:2]) == (B, C)
+    if zfs is not None:
+        assert len(zfs) == n
+        for z, zf in zip(zs, zfs):
+            _req(zf, torch.float32, 4, "zf")
+            assert zf.shape == z.shape
+    H, W = int(H), int(W)
+    dev = zs[0].device
+    maxprob = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    argmax = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    if hist is None:
+        hist = torch.zeros((C, NBINS), dtype=torch.int32, device=dev)
+    else:
+        _req(hist, torch.int32, 2, "hist")
+        assert tuple(hist.shape) == (C, NBINS)
+    if B:
+        lib = _lib.load()
+        if not plabel_pass1_tta_supported(C, n):
+            raise _lib.HiastLibraryError("hiast_plabel_pass1_tta: %d classes / %d scales are outside what the kernel is built "
+                                         "for (classes %s, at most %d scales)" % (C, n, TTA_FUSED_CLASSES, TTA_FUSED_MAX_SCALES))
+        # the scattered counting copy of the histogram: one per device, stream and class count, as plabel_pass1 keeps it
+        key = (zs[0].get_device(), torch.cuda.current_stream(dev).cuda_stream, C)
+        ws = _pass1_tta_ws.get(key)
+        if len(_pass1_tta_ws) > 16 and ws is None:
+            _pass1_tta_ws.clear()
+        if ws is None:
+            ws = torch.empty(lib.hiast_plabel_pass1_tta_workspace_bytes(C) // 4, dtype=torch.int32, device=dev)
+            _pass1_tta_ws[key] = ws
+        vp = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        iv = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+        check(lib.hiast_plabel_pass1_tta(vp(zs), vp(zfs) if zfs is not None else None, iv([z.shape[2] for z in zs]),
+                                         iv([z.shape[3] for z in zs]), iv([s[0] for s in sizes]), iv([s[1] for s in sizes]),
+                                         n, B, C, H, W, _ptr(maxprob), _ptr(argmax), _ptr(hist), _ptr(ws), ws.numel() * 4,
+                                         _stream()), "hiast_plabel_pass1_tta")
+    return maxprob, argmax, hist
+
+
 # ------------------------------------------------------------------------------- K15 discriminator input
 def dinput_fwd(logits_lr, H, W, entropy):
     """low-res logits [B,C,h,w] -> softmax (or weighted self-information) map [B,C,H,W] of the upsampled logits"""

@@ -145,6 +145,9 @@ pseudo_policy:
   ias: {alpha: 0.2, beta: 0.9, gamma: 8.0}
   cbst: {p: 0.2, sample_interval: 4}
   ct: {threshold: 0.9}
+  tta: {resize_sizes: [], is_flip: false}   # (not in the reference) pass 1 averages the softmax over these [height, width] views (and
+                                  # their mirror images) as the Validator does; is_flip alone = resize_size + its mirror image;
+                                  # labels are always written at resize_size.  Both at their defaults: the single-view pass 1
 train:
   batch_size: 4
   lr: 0.0001

@@ -11,7 +11,9 @@ What changed under the same interface (`PSEUDO_POLICY[type](cfg).run()`, same ar
   * select / count / Σprob is a second HIP kernel (pass 2);
   * with torch.distributed initialised, images of a global batch are split over ranks and the
     histograms / class sums are all-reduced (RCCL): the result equals the single-process run with
-    batch_size = world * local_batch on the same image order.
+    batch_size = world * local_batch on the same image order;
+  * (not in the reference) `pseudo_policy.tta`: pass 1 averages the softmax over several resized views and their mirror
+    images, as the Validator does, in one HIP kernel (hiast_plabel_pass1_tta); off by default.
 """
 import json
 import os
@@ -55,10 +57,65 @@ class ShardedBatchSampler(Sampler):
 class HipPlabelEngine:
     """Device side of one generator step (the HIP kernels); no CPU path."""
 
-    def __init__(self, model, device, num_classes):
+    def __init__(self, model, device, num_classes, sizes=None, flip=False):
+        """sizes, flip: the views pass 1 averages over (pseudo_policy.tta; none = one forward at the frame's own size)"""
         if torch.device(device).type != "cuda":
             raise RuntimeError("HipPlabelEngine runs on the HIP device only (no CPU path); got %r" % (device,))
         self.model, self.device, self.C = model, device, num_classes
+        self.set_views(sizes, flip)
+
+    def set_views(self, sizes=None, flip=False):
+        """the view list of pass 1: `sizes` = [height, width] each frame is resized to (one forward each), flip = the mirror
+        image of every view as well.  An empty list with flip is the frame at its own size plus its mirror image; an empty
+        list without flip is the single-view pass 1 (hiast_plabel_pass1).  With views set the label and its confidence are the
+        validator's: argmax and mean over the views of the summed softmax (hiast_plabel_pass1_tta); there is no fallback."""
+        from hiast_amd import _lib, kernels as K
+        sizes = [(int(s[0]), int(s[1])) for s in (sizes or [])]
+        for s in sizes:
+            assert 0 < s[0] <= s[1], "each tta.resize_sizes entry is [height, width] with height <= width, such as [512, 1024]"
+        self.sizes, self.flip = sizes, bool(flip)
+        self.views = bool(sizes) or self.flip
+        if self.views and not K.plabel_pass1_tta_supported(self.C, max(1, len(sizes))):
+            raise _lib.HiastLibraryError(
+                "pseudo_policy.tta: hiast_plabel_pass1_tta is built for %s classes and at most %d sizes; got %d classes, %d sizes"
+                % (K.TTA_FUSED_CLASSES, K.TTA_FUSED_MAX_SCALES, self.C, len(sizes)))
+
+    def view_sizes(self, H, W):
+        """the sizes a batch of H x W frames is forwarded at"""
+        return list(self.sizes) if self.sizes else [(int(H), int(W))]
+
+    def _forward(self, x, side_by_side):
+        """low-res logits of one inference forward, in a tensor of their own"""
+        import contextlib
+        from hiast_amd import kernels as K
+        if getattr(self, "_fwd", None) is None or self._fwd.model is not self.model:
+            self._fwd = HF.GraphedEval(self.model, None)
+        with (K.cosched() if side_by_side else contextlib.nullcontext()):
+            z = self._fwd(x)
+        # (a replayed graph hands out its own output buffer, which the next forward of the same shape overwrites)
+        return z.clone() if self._fwd.wants_graph(x) else z.contiguous()
+
+    def _pass1_views(self, x, side_by_side):
+        """forwards of every view of the normalised batch x + hiast_plabel_pass1_tta -> (maxprob, argmax, hist).  The views are
+        built the way the Validator builds them (validator._resample, torch.flip), and a view shares a forward with its
+        mirror image under the Validator's condition only (1/8 map of 4096 pixels or more: the same kernels run, the logits
+        are bit for bit those of two forwards; HIAST_VAL_BATCH_FLIP=0: always two forwards)."""
+        from hiast_amd import kernels as K
+        H, W = x.shape[2:]
+        n = x.shape[0]
+        zs, zfs, sizes = [], [], self.view_sizes(H, W)
+        for size in sizes:
+            v = x.float() if tuple(size) == (H, W) else HF.upsample_bilinear_ac(x.float(), size)
+            if (self.flip and (size[0] // 8) * (size[1] // 8) >= 4096
+                    and os.environ.get("HIAST_VAL_BATCH_FLIP", "1") != "0"):
+                z2 = self._forward(torch.cat([v, torch.flip(v, dims=[3])], 0), side_by_side)
+                zs.append(z2[:n].contiguous())
+                zfs.append(z2[n:].contiguous())
+            else:
+                zs.append(self._forward(v, side_by_side))
+                if self.flip:
+                    zfs.append(self._forward(torch.flip(v, dims=[3]), side_by_side))
+        return K.plabel_pass1_tta(zs, zfs if self.flip else None, sizes, H, W)
 
     @staticmethod
     def _equiv(n_images, hw):
@@ -85,7 +142,11 @@ class HipPlabelEngine:
         same order per element), PROVIDED the launch size does not change which kernel runs: the register-resident-weight kernels
         (xconv / xconv2) take a 1x1 launch from 4096 output rows on and differ from the tile kernel in summation order (2e-5).
         Frames whose 1/8-resolution map has fewer than 4096 pixels (below 512 x 512) would cross that gate by being grouped, so
-        they are not grouped (nor is anything when the frame size is unknown).  HIAST_GEN_GROUP=1: one forward per loader batch."""
+        they are not grouped (nor is anything when the frame size is unknown).  HIAST_GEN_GROUP=1: one forward per loader batch.
+        With views set (set_views) every batch has its forwards to itself: views of different sizes cannot share a launch
+        without crossing that gate."""
+        if self.views:
+            return 1
         if not hw or (int(hw[0]) // 8) * (int(hw[1]) // 8) < 4096:
             return 1
         env = os.environ.get("HIAST_GEN_GROUP", "")
@@ -100,8 +161,8 @@ class HipPlabelEngine:
     @torch.no_grad()
     def begin_group(self, batches, lane=None):
         """begin() for several consecutive loader batches with ONE forward over their images -> one state per batch (in order)"""
-        if len(batches) == 1:
-            return [self.begin(batches[0], lane)]
+        if len(batches) == 1 or self.views:
+            return [self.begin(b, lane) for b in batches]
         live = [b for b in batches if b is not None and b.shape[0] > 0]
         if len(live) <= 1 or len({tuple(b.shape[1:]) for b in live}) != 1 or len({b.dtype for b in live}) != 1:
             return [self.begin(b, lane) for b in batches]          # (ragged image sizes: no shared launch)
@@ -184,6 +245,12 @@ class HipPlabelEngine:
             if imgs.dtype == torch.uint8:        # dataset.device_transform: ToTensor + Normalize here, on the device
                 from hiast_amd.sseg.datasets.utils import MEAN, STD
                 imgs = K.normalize_u8(imgs, MEAN, STD)
+            if self.views:
+                st["mp"], st["am"], st["hist"] = self._pass1_views(imgs, side_by_side)
+                st["ev"] = torch.cuda.Event()
+                st["ev"].record()
+                return st
+            # (no views: today's single forward and hiast_plabel_pass1, untouched)
             from hiast_amd import functional as HF
             if getattr(self, "_fwd", None) is None or self._fwd.model is not self.model:
                 # the fp32-class inference forward (two sub-batches on two streams for 8 or more images); HIAST_GRAPH_EVAL=1:
@@ -260,6 +327,14 @@ class HipPlabelEngine:
         return plbl, count, sfx
 
 
+def tta_views(pp):
+    """pseudo_policy.tta -> (sizes, flip) for HipPlabelEngine; ([], False) = off"""
+    t = pp.get("tta")                  # (a config dumped before the key existed has none)
+    if t is None:
+        return [], False
+    return [[int(s[0]), int(s[1])] for s in (t.resize_sizes or [])], bool(t.is_flip)
+
+
 class BasePseudoGenerator:
 
     def __init__(self, cfg, engine=None, dataset=None):
@@ -309,7 +384,9 @@ class BasePseudoGenerator:
         if engine is None:
             device = utils.get_device()
             model = utils.load_model(self.cfg, resume_from=pp.resume_from).to(device).eval()
-            engine = HipPlabelEngine(model, device, self.cfg.dataset.num_classes)
+            engine = HipPlabelEngine(model, device, self.cfg.dataset.num_classes, *tta_views(pp))
+        elif any(tta_views(pp)) and hasattr(engine, "set_views"):
+            engine.set_views(*tta_views(pp))
         self.engine = engine
         self.pseudo_label_save_dir = pp.save_dir
         assert self.pseudo_label_save_dir is not None and (

@@ -137,6 +137,24 @@ int hiast_tta_fused(const float* const* z, const float* const* zf, const int* hs
                     const int* Ws, int n_scales, int B, int C, int H, int W, float* probsum, uint8_t* label,
                     hiast_stream_t stream);
 
+/* ---- K3c: pseudo-label pass 1 over several views (multi-scale + flip) -------------------
+ * K16's view averaging with K3's outputs, from the LOW-RES head outputs of every (scale, flip) forward.
+ * z, zf, hs, ws, Hs, Ws as for hiast_tta_fused (zf NULL = no mirror views; a zf with a NULL entry is HIAST_E_ARG).
+ * Per native pixel:
+ *   tot[c]  = the per-class probability sum of hiast_tta_fused (same operations in the same order)
+ *   argmax  = the first class with the largest tot[c]                      (the validator's label)
+ *   n_views = n_scales * (zf ? 2 : 1)
+ *   maxprob = fminf(tot[argmax] / (float)n_views, 1.0f)                    (IEEE fp32 division: the mean probability over the
+ *             views; the sum can exceed n_views by rounding — the clamp keeps the fp16 bin at most 0x3C00, the last one)
+ *   hist[argmax][fp16 bits of maxprob] += 1                                (bins < HIAST_NBINS, as pass 1)
+ * -> maxprob f32 [B,H,W], argmax u8 [B,H,W], hist u32 [C,HIAST_NBINS] accumulated.  C in {19, 16, 9, 2}.
+ * workspace (optional, hiast_plabel_pass1_tta_workspace_bytes(C) bytes, 4-byte aligned, zeroed by the call): the scattered
+ * counting copy of pass 1 plus a merge launch; NULL = count straight into hist. */
+size_t hiast_plabel_pass1_tta_workspace_bytes(int C);
+int hiast_plabel_pass1_tta(const float* const* z, const float* const* zf, const int* hs, const int* ws, const int* Hs,
+                           const int* Ws, int n_scales, int B, int C, int H, int W, float* maxprob, uint8_t* argmax,
+                           uint32_t* hist, void* workspace, size_t workspace_bytes, hiast_stream_t stream);
+
 /* ---- K5-K8: fused self-training loss ------------------------------------------------
  * SelfTrainingSegmentor.compute_loss, self_training_segmentor.py:30-53 with
  * losses.py:32-36 (CE), :39-65,75-89 (SoftCE on a region), _kld :153-163, _entropy :140-150,
