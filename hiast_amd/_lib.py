@@ -105,6 +105,8 @@ SIGNATURES = {
     "hiast_aug2_table_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
     "hiast_aug2_colour_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
     "hiast_aug2_blur_u8": (c_int, [c_vp] * 5 + [c_int] * 3 + [c_vp]),
+    "hiast_aug3_fda_workspace_bytes": (c_sz, [c_int] * 3),
+    "hiast_aug3_fda_u8": (c_int, [c_vp] * 6 + [c_int] * 3 + [c_vp]),
     "hiast_adam_prepare": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "hiast_adam_step": (c_int, [c_vp, c_vp, c_vp, c_int, ctypes.c_double, ctypes.c_double, c_f32, c_f32, c_vp, c_vp]),
     "hiast_sgd_step": (c_int, [c_vp, c_vp, c_vp, c_int, c_f32, c_f32, c_vp, c_vp]),

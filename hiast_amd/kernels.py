@@ -701,6 +701,8 @@ def multi_copy(plan):
 AUG_REC_WORDS, AUG_MAX_OPS = 20, 8
 AUG_OPS_WORDS = 4 + 2 * AUG_MAX_OPS
 AUG_MAX_KSIZE = 41
+AUG_OP_BLUR, AUG_OP_FDA = 7, 8
+AUG_FDA_MAX_BORDER, AUG_FDA_BORDER_SHIFT, AUG_FDA_MIN_SIDE = 2, 40, 8
 
 
 def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
@@ -755,7 +757,7 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
             if o[0] != 0 or not 0 <= o[2] <= AUG_MAX_OPS:
                 raise ValueError("device_aug: sample %d view %d: kind %d with %d ops" % (b, k, o[0], o[2]))
             types = [o[4 + 2 * i] for i in range(o[2])]
-            if any(t not in (1, 2, 3, 4, 5, 6, 7) for t in types) or (max(types, default=0) <= 3 and types.count(3) > 1):
+            if any(t not in (1, 2, 3, 4, 5, 6, 7, 8) for t in types) or (max(types, default=0) <= 3 and types.count(3) > 1):
                 raise ValueError("device_aug: sample %d view %d: op types %s" % (b, k, types))
             for i, t in enumerate(types):
                 par = o[5 + 2 * i]
@@ -775,6 +777,11 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
                     w = tabs[off:off + ksize].view(np.float32)
                     if not (np.isfinite(w).all() and np.array_equal(w, w[::-1])):
                         raise ValueError("device_aug: sample %d view %d: blur weights not finite and symmetric" % (b, k))
+                elif t == 8:               # FDA: blob offset of the target view | border << 40
+                    border, off = par >> AUG_FDA_BORDER_SHIFT, par & ((1 << AUG_FDA_BORDER_SHIFT) - 1)
+                    if not (0 <= border <= AUG_FDA_MAX_BORDER and min(oh, ow) >= AUG_FDA_MIN_SIDE):
+                        raise ValueError("device_aug: sample %d view %d: FDA of border %d on %dx%d" % (b, k, border, oh, ow))
+                    inside(off, oh * ow * 3, blob_n, "view %d FDA target" % k, b)
 
 
 def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch):
@@ -816,7 +823,8 @@ def aug_colour_u8(img_u8, ops, blob, equalize=True):
 
 def _aug_segments(ops_view):
     """one view's op rows (numpy int64 [B, 20]) -> int32 [R, B, 4] = (from, to, stat, blur) per launch round and sample
-    (include/hiast_hip.h, K15b): a segment ends before a second table op (Equalize 3 / contrast 4) and after a blur (7)"""
+    (include/hiast_hip.h, K15b, K15c): a segment ends before a second table op (Equalize 3 / contrast 4) and after a
+    blur (7) or an FDA (8), whose index stands in the fourth word"""
     B = ops_view.shape[0]
     rounds = []
     pos = [0] * B
@@ -827,12 +835,12 @@ def _aug_segments(ops_view):
             i, stat = pos[b], -1
             while i < n[b]:
                 t = int(ops_view[b, 4 + 2 * i])
-                if t == 7 or (t in (3, 4) and stat >= 0):
+                if t in (7, 8) or (t in (3, 4) and stat >= 0):
                     break
                 if t in (3, 4):
                     stat = i
                 i += 1
-            blur = i if i < n[b] and int(ops_view[b, 4 + 2 * i]) == 7 else -1
+            blur = i if i < n[b] and int(ops_view[b, 4 + 2 * i]) in (7, 8) else -1
             seg[b] = (pos[b], i, stat, blur)
             pos[b] = i + (blur >= 0)
         rounds.append(seg)
@@ -864,12 +872,51 @@ def aug2_view_u8(img_u8, ops, ops_h, blob, tabs):
         if r == 0 or (segs_h[r, :, 1] > segs_h[r, :, 0]).any():
             check(lib.hiast_aug2_colour_u8(_ptr(ops), _ptr(sg), _ptr(blob), _ptr(table), _ptr(src), _ptr(out), B, H * W,
                                            _stream()), "hiast_aug2_colour_u8")
-        if (segs_h[r, :, 3] >= 0).any():
+        closing = [int(ops_h[b, 4 + 2 * i]) for b, i in enumerate(segs_h[r, :, 3]) if i >= 0]
+        if AUG_OP_BLUR in closing:
             if tmp is None:
                 tmp = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
             check(lib.hiast_aug2_blur_u8(_ptr(ops), _ptr(sg), _ptr(tabs), _ptr(out), _ptr(tmp), B, H, W, _stream()),
                   "hiast_aug2_blur_u8")
+        if AUG_OP_FDA in closing:
+            aug3_fda_u8(out, ops, sg, blob)
     return out
+
+
+_fda_trig_cache = {}
+
+
+def _fda_trig(H, W, device):
+    """float64 cos[H], sin[H], cos[W], sin[W] of 2 pi j / n on the device, built on the host once per view shape (a batch's
+    views share one shape), as the resampler's coefficient tables are"""
+    key = (H, W, str(device))
+    t = _fda_trig_cache.get(key)
+    if t is None:
+        from hiast_amd.sseg.datasets.device_aug import fda_trig
+        if len(_fda_trig_cache) >= 16:
+            _fda_trig_cache.clear()
+        t = torch.from_numpy(np.concatenate(fda_trig(H) + fda_trig(W))).to(device)
+        _fda_trig_cache[key] = t
+    return t
+
+
+def aug3_fda_u8(img_u8, ops, seg, blob):
+    """the FDA op that closes each sample's segment (ops int64 [B, 20], seg int32 [B, 4], blob: device tensors, bounds-checked
+    by the caller), IN PLACE on uint8 [B, H, W, 3]; a sample whose segment is closed by no FDA op is not touched"""
+    _req(img_u8, torch.uint8, 4, "img_u8")
+    _req(ops, torch.int64, 2, "ops")
+    _req(seg, torch.int32, 2, "seg")
+    _req(blob, torch.uint8, 1, "blob")
+    B, H, W, three = img_u8.shape
+    assert three == 3 and tuple(ops.shape) == (B, AUG_OPS_WORDS) and tuple(seg.shape) == (B, 4)
+    if min(H, W) < AUG_FDA_MIN_SIDE:
+        raise ValueError("aug3_fda_u8: a view of %dx%d (sides of at least %d)" % (H, W, AUG_FDA_MIN_SIDE))
+    lib = _lib.load()
+    trig = _fda_trig(H, W, img_u8.device)
+    ws = torch.empty((lib.hiast_aug3_fda_workspace_bytes(B, H, W) // 8,), dtype=torch.float64, device=img_u8.device)
+    check(lib.hiast_aug3_fda_u8(_ptr(ops), _ptr(seg), _ptr(blob), _ptr(trig), _ptr(img_u8), _ptr(ws), B, H, W, _stream()),
+          "hiast_aug3_fda_u8")
+    return img_u8
 
 
 def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):

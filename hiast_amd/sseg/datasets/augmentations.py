@@ -31,6 +31,10 @@ def _resize_img(img, h, w):
     return np.asarray(Image.fromarray(img).resize((w, h), Image.BILINEAR))
 
 
+def _read_rgb(path):
+    return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+
+
 def _resize_mask(m, h, w):
     return np.asarray(Image.fromarray(m).resize((w, h), Image.NEAREST))
 
@@ -427,14 +431,17 @@ class FDA(_Aug):
 
     def __init__(self, reference_images, beta_limit=0.1, read_fn=None, p=0.5):
         self.refs, self.beta, self.p = list(reference_images), (0, beta_limit) if np.isscalar(beta_limit) else tuple(beta_limit), p
-        self.read_fn = read_fn or (lambda path: np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8))
+        self.read_fn = read_fn or _read_rgb
+
+    def draw(self):
+        """the draws of params() without the read -> (beta, path of the reference image).  Draw order of albumentations
+        1.0.3: get_params() (beta) runs before get_params_dependent_on_targets() (the reference image)"""
+        beta = random.uniform(self.beta[0], self.beta[1])
+        return beta, random.choice(self.refs)
 
     def params(self, image):
-        # draw order of albumentations 1.0.3: get_params() (beta) runs before get_params_dependent_on_targets() (the
-        # reference image)
-        beta = random.uniform(self.beta[0], self.beta[1])
-        target = self.read_fn(random.choice(self.refs))
-        target = _resize_img(target, image.shape[0], image.shape[1])
+        beta, path = self.draw()
+        target = _resize_img(self.read_fn(path), image.shape[0], image.shape[1])
         return {"target": target, "beta": beta}
 
     def apply(self, image, masks, target, beta):

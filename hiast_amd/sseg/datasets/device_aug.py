@@ -11,9 +11,13 @@ drawing; resampling and recolouring run on the device (hiast_amd/csrc/sample_aug
     assemble_device_batch(batch, device)      -> what utils.to_device_batch returns (normalised float32 CHW views, labels)
 
 A view plan is {"ops": [...], "host": bool}; ops are ("geom", Geometry), ("lut", uint8[256]), ("gray",), ("equalize",)
-and ("host", name).  ColorJitter, GaussianBlur and FDA have no device form (PIL's C HSV conversion, scipy's float64
-correlate, an FFT): a sample whose plan holds one of them is run through augmentations.aug() by the worker as before
-and handed over as finished uint8 views (`needs_host`).
+and ("host", name).  At level 1 ColorJitter, GaussianBlur and FDA have no device form (PIL's C HSV conversion, scipy's
+float64 correlate, an FFT): a sample whose plan holds one of them is run through augmentations.aug() by the worker as
+before and handed over as finished uint8 views (`needs_host`).
+
+plan_sample(level=2) plans ColorJitter and GaussianBlur too; plan_sample(level=3) also FDA, as ("fda", path, border): the
+sparse-DFT form `fda_u8` — the view plus the inverse DFT of the at most 25 centre bins whose amplitude the reference
+image replaces.  The worker decodes and resizes the reference image (pack_sample); it travels in the uint8 blob.
 
 Resampling restates Pillow's two-pass 8-bit resample in integers (ImagingResample: per-axis coefficient tables in
 float64, rounded to 22-bit fixed point, horizontal pass rounded to uint8, then the vertical pass) and its affine
@@ -32,6 +36,8 @@ HOST_ONLY = (A.ColorJitter, A.GaussianBlur, A.FDA)
 OP_LUT, OP_GRAY, OP_EQUALIZE = 1, 2, 3
 OP_CONTRAST, OP_SAT, OP_HUE, OP_BLUR = 4, 5, 6, 7        # level 2 (plan_sample(level=2)): ColorJitter's steps, GaussianBlur
 MAX_KSIZE = 41
+OP_FDA = 8                                               # level 3: blob offset of the target view | border << 40
+FDA_MAX_BORDER, FDA_BORDER_SHIFT, FDA_MIN_SIDE = 2, 40, 8
 
 
 # ------------------------------------------------------------------------------------------------- tables
@@ -187,14 +193,18 @@ class _Walker:
         self.geom_open = True                    # no pixel op recorded yet: geometry may still be folded into view 0's op
         self.ops = []
         self.host = False
-        self.stop = False                        # FDA: its params() read the image — the draws cannot be finished here
+        self.stop = False                        # FDA below level 3: its params() read the image — the draws stop here
+        self.readers = {}                        # level 3: reference image path -> the read_fn of the FDA that drew it
 
     def begin_view(self):
         self.ops = []
 
     def end_view(self):
         self._close_geometry()
-        return {"ops": self.ops, "host": any(o[0] == "host" for o in self.ops)}
+        view = {"ops": self.ops, "host": any(o[0] == "host" for o in self.ops)}
+        if any(o[0] == "fda" for o in self.ops):
+            view["readers"] = {o[1]: self.readers[o[1]] for o in self.ops if o[0] == "fda"}
+        return view
 
     def _close_geometry(self):
         if self.geom_open:
@@ -227,14 +237,24 @@ class _Walker:
                 for c in t.transforms:
                     self.walk(c)
             return
-        if isinstance(t, A.FDA):
+        if isinstance(t, A.FDA) and self.level < 3:
             self._pixel_op(("host", "FDA"))
             self.stop = True
             return
         if not random.random() < t.p:
             return
-        params = t.params(None)
         g = self.geom
+        if isinstance(t, A.FDA):                 # level 3: the draws of params() without the read
+            beta, path = t.draw()
+            h, w = g.shape()
+            border = int(np.floor(min(h, w) * beta))
+            if border > FDA_MAX_BORDER or min(h, w) < FDA_MIN_SIDE:      # (a large beta_limit: the host's FFT)
+                self._pixel_op(("host", "FDA"))
+            else:
+                self.readers[path] = t.read_fn
+                self._pixel_op(("fda", path, border))
+            return
+        params = t.params(None)
         if isinstance(t, A.HorizontalFlip):
             self._geom_op(self.geom_open and g.do_flip())
         elif isinstance(t, A.Resize):
@@ -299,7 +319,9 @@ def plan_sample(aug_fun, in_shape, index=None, level=1):
     """-> list of view plans (one per view; a single aug gives a list of one).  Consumes exactly the draws
     augmentations.aug(aug_fun, img, lbl, index) consumes unless the plan `needs_host` through an FDA, whose parameters read
     the image: the caller restores the state it saved and runs aug() (see BaseDataset).  level 2: ColorJitter and
-    GaussianBlur are plan ops too (("contrast", f), ("sat", f), ("hue", shift), ("blur", weights))."""
+    GaussianBlur are plan ops too (("contrast", f), ("sat", f), ("hue", shift), ("blur", weights)).  level 3: FDA is the
+    plan op ("fda", path, border), drawn as A.FDA.params draws it but without opening the file — the draws are always
+    those of aug(); border > 2, or a view with a side below 8, stays ("host", "FDA")."""
     if index is not None:
         random.seed(index)
     w = _Walker(in_shape, level)
@@ -462,9 +484,92 @@ def blur_u8(img, w):
     return np.clip(np.rint(x), 0, 255).astype(np.uint8)
 
 
-def execute_colour_host(ops, img):
+def fda_trig(n):
+    """cos, sin of 2 pi j / n for j < n (float64): the table every layer reads, indexed by the angle AFTER its integer mod"""
+    t = 2.0 * np.pi * np.arange(n, dtype=np.float64) / np.float64(n)
+    return np.cos(t), np.sin(t)
+
+
+def fda_u8(img, target, border):
+    """the FDA op: trunc(clip(fda_f64(img, target, border), 0, 255)) on uint8 [H, W, 3] — the definition the executor, the
+    kernels and the tests are pinned to.  One deliberate difference from the host FFT: target == img returns img exactly
+    (see fda_f64)."""
+    return np.clip(fda_f64(img, target, border), 0, 255).astype(np.uint8)
+
+
+def fda_f64(img, target, border):
+    """the values fda_u8 truncates: augmentations.fourier_domain_adaptation(img, target, beta) with
+    border = floor(min(H, W) * beta) in its sparse-DFT form, float64: the FFT is linear and every bin outside the centre
+    square keeps its value, so per channel c, over the bins (ky, kx) with |ky|, |kx| <= border,
+        S = sum_y sum_x img[y, x, c] exp(-2 pi i (((ky y) mod H) / H + ((kx x) mod W) / W)),  T likewise over target,
+        D = (|T| - |S|) S / |S|                                  (S == 0: the phase is 1, as np.angle(0) == 0)
+        f = img + sum_bins Re(D exp(+2 pi i ...)) / (H W),       out = trunc(clip(f, 0, 255)).
+    The input is real: a bin and its conjugate partner are computed once (1, 5 or 13 bins).  With
+    e(y) = (1, cos ty, sin ty, cos 2ty, sin 2ty) and r(x) likewise, every bin sum is a signed pair of entries of
+    G = e^T img r, and the correction is e C r^T with C built from D / (H W): the form the kernels compute.
+    The ONE deliberate difference from the host FFT: with target == img, D is exactly 0 and this form returns img
+    exactly; the host's complex64 FFT round trip can move a byte down by one there (and, for any target, wherever f is
+    within about 1e-3 of an integer: the host is the noisy party at those knife edges)."""
+    img, target = np.asarray(img), np.asarray(target)
+    H, W = img.shape[:2]
+    nb = int(border)
+    if img.dtype != np.uint8 or target.shape != img.shape or img.ndim != 3 or not 0 <= nb <= FDA_MAX_BORDER \
+            or min(H, W) < FDA_MIN_SIDE:
+        raise ValueError("fda_u8: uint8 [H, W, C] image and target of one shape, border 0..%d, sides >= %d"
+                         % (FDA_MAX_BORDER, FDA_MIN_SIDE))
+    nc = 1 + 2 * nb
+
+    def basis(n):
+        cs, sn = fda_trig(n)
+        rows = [np.ones(n)]
+        for k in range(1, nb + 1):
+            a = (k * np.arange(n)) % n
+            rows += [cs[a], sn[a]]
+        return np.stack(rows)                                         # [nc, n]
+    E, R = basis(H), basis(W)
+    f = np.empty(img.shape, np.float64)
+    hw = np.float64(H) * np.float64(W)
+    for c in range(img.shape[2]):
+        v = img[..., c].astype(np.float64)
+        gs = E @ (v @ R.T)                                            # rows reduced along x, then the row factors
+        gt = E @ (target[..., c].astype(np.float64) @ R.T)
+        cf = np.zeros((nc, nc))
+        for ky in range(0, nb + 1):
+            for kx in range(-nb if ky else 0, nb + 1):
+                ax, sg = abs(kx), (-1.0 if kx < 0 else 1.0)
+                ci, si, cj, sj = (2 * ky - 1 if ky else 0), 2 * ky, (2 * ax - 1 if ax else 0), 2 * ax
+
+                def bin_of(g):
+                    re = g[ci, cj] - (sg * g[si, sj] if ky and ax else 0.0)
+                    im = -((g[si, cj] if ky else 0.0) + (sg * g[ci, sj] if ax else 0.0))
+                    return re, im
+                (sr, sim), (tr, tim) = bin_of(gs), bin_of(gt)
+                ms, mt = np.sqrt(sr * sr + sim * sim), np.sqrt(tr * tr + tim * tim)
+                pr, pi = (1.0, 0.0) if ms == 0.0 else (sr / ms, sim / ms)
+                wgt = 2.0 if (ky or ax) else 1.0                      # the bin and its conjugate partner
+                dr, di = wgt * ((mt - ms) * pr / hw), wgt * ((mt - ms) * pi / hw)
+                cf[ci, cj] += dr
+                if ky and ax:
+                    cf[si, sj] -= sg * dr
+                if ky:
+                    cf[si, cj] -= di
+                if ax:
+                    cf[ci, sj] -= sg * di
+        f[..., c] = v + (E.T @ cf) @ R
+    return f
+
+
+def fda_target(path, shape, read_fn=None):
+    """the reference image of an ("fda", path, border) op as the host transform sees it: decoded, resized with Pillow"""
+    return np.array(A._resize_img((read_fn or A._read_rgb)(path), int(shape[0]), int(shape[1])), np.uint8, order="C")
+
+
+def execute_colour_host(ops, img, readers=None):
+    """readers: {path: read_fn} of the view's FDA ops (plan_sample(level=3) records them in the view plan)"""
     for op in ops:
-        if op[0] == "contrast":
+        if op[0] == "fda":
+            img = fda_u8(img, fda_target(op[1], img.shape, (readers or {}).get(op[1])), op[2])
+        elif op[0] == "contrast":
             img = contrast_lut(img, op[1])[img]
         elif op[0] == "sat":
             img = saturation_u8(img, op[1])
@@ -497,7 +602,7 @@ def execute_plan_host(plan, img, lbl, paste=None, sliced=False):
     cur, label = execute_geometry_host(g, img, lbl, paste)
     imgs, lbls = [], []
     for k, v in enumerate(plan):
-        cur = execute_colour_host(v["ops"][1:] if k == 0 else v["ops"], cur)
+        cur = execute_colour_host(v["ops"][1:] if k == 0 else v["ops"], cur, v.get("readers"))
         imgs.append(cur)
         lbls.append(label)
     return imgs, lbls
@@ -536,8 +641,14 @@ class _Blob:
 
 
 def pack_sample(plan, raw_img, raw_lbl, paste=None):
-    """what a worker returns for a planned sample: {"plan", "raw"} with the slices of plan_window(plan)"""
+    """what a worker returns for a planned sample: {"plan", "raw"} with the slices of plan_window(plan); the reference
+    image of every FDA op is decoded and resized to the view here, in the worker (raw["fda"], in op order)"""
     raw = {"img": torch.from_numpy(np.ascontiguousarray(raw_img)), "lbl": torch.from_numpy(np.ascontiguousarray(raw_lbl))}
+    out_shape = plan[0]["ops"][0][1].out
+    fda = [torch.from_numpy(fda_target(op[1], out_shape, v.get("readers", {}).get(op[1])))
+           for v in plan for op in v["ops"] if op[0] == "fda"]
+    if fda:
+        raw["fda"] = fda
     if paste is not None:
         raw["paste_img"] = torch.from_numpy(np.ascontiguousarray(paste[0]))
         raw["paste_lbl"] = torch.from_numpy(np.ascontiguousarray(paste[1]))
@@ -593,6 +704,7 @@ def build_batch_tables(samples):
         r[R_VLO], r[R_VN], r[R_VK], r[R_VT] = tabs.add(g.vlo), tabs.add(g.vn), tabs.add(g.vk), g.vk.shape[1]
         r[R_NX], r[R_NY] = tabs.add(g.nx), tabs.add(g.ny)
         max_ch = max(max_ch, ch)
+        fda = iter(raw.get("fda", ()))
         for k, v in enumerate(s["plan"]):
             row = ops[k, b]
             row[0] = KIND_PLAN
@@ -612,6 +724,11 @@ def build_batch_tables(samples):
                 elif op[0] == "blur":                        # float32 weights (as bits) in the int32 table blob
                     w = np.ascontiguousarray(op[1], np.float32)
                     row[4 + 2 * i], row[5 + 2 * i] = OP_BLUR, tabs.add(w.view(np.int32)) | (len(w) << 32)
+                elif op[0] == "fda":                         # the target view travels as CopyPaste's source frame does
+                    t = next(fda).numpy()
+                    if tuple(t.shape) != (out[0], out[1], 3) or not 0 <= int(op[2]) <= FDA_MAX_BORDER:
+                        raise ValueError("device_aug: FDA target %s for a view of %s, border %r" % (tuple(t.shape), out, op[2]))
+                    row[4 + 2 * i], row[5 + 2 * i] = OP_FDA, blob.add(t) | (int(op[2]) << FDA_BORDER_SHIFT)
                 else:
                     raise ValueError("op %r has no device form" % (op[0],))
                 row[2] = i + 1

@@ -132,7 +132,7 @@ dataset:
   decoded_cache_dir: null         # (not in the reference) directory for decoded uint8 arrays, e.g. /dev/shm/hiast_cache
   decoded_cache_gb: 16.0
   device_aug: false               # (not in the reference) workers plan, the device crops / resamples / recolours (device_aug.py)
-  device_aug_level: 1             # with device_aug: 2 = ColorJitter and GaussianBlur run on the device too (1: those samples come finished from the workers)
+  device_aug_level: 1             # with device_aug: 2 = ColorJitter and GaussianBlur run on the device too (1: those samples come finished from the workers); 3 = 2 + FDA (sparse-DFT form)
   source: {type: null, json_path: null, image_dir: null, aug_type: []}
   target: {type: null, json_path: null, image_dir: null, pseudo_dir: null, aug_type: []}
   val: {type: null, json_path: null, image_dir: null, resize_size: null}

@@ -171,12 +171,14 @@ class BaseTrainer:
         # decision and hand over the crop window's bytes + the plan, the device resamples and recolours (device_aug.py)
         # cfg.dataset.device_aug_level: 2 / HIAST_DEVICE_AUG=2: ColorJitter and GaussianBlur are planned and run on the
         # device too (no 'CCA' / 'SCA' sample falls back to the worker path)
+        # cfg.dataset.device_aug_level: 3 / HIAST_DEVICE_AUG=3: level 2 + FDA in its sparse-DFT form (no 'FDA-*' sample
+        # falls back unless geometry follows the FDA)
         env = os.environ.get("HIAST_DEVICE_AUG", "0")
         ds.device_aug = (ds.device_transform and shuffle and drop_last
-                         and (bool(getattr(self.cfg.dataset, "device_aug", False)) or env in ("1", "2")))
-        ds.device_aug_level = 2 if env == "2" else int(getattr(self.cfg.dataset, "device_aug_level", 1))
-        if ds.device_aug_level not in (1, 2):
-            raise ValueError("dataset.device_aug_level is 1 or 2, not %r" % (ds.device_aug_level,))
+                         and (bool(getattr(self.cfg.dataset, "device_aug", False)) or env in ("1", "2", "3")))
+        ds.device_aug_level = int(env) if env in ("2", "3") else int(getattr(self.cfg.dataset, "device_aug_level", 1))
+        if ds.device_aug_level not in (1, 2, 3):
+            raise ValueError("dataset.device_aug_level is 1, 2 or 3, not %r" % (ds.device_aug_level,))
         if ds.device_aug:
             from hiast_amd.sseg.datasets import device_aug
             kw["collate_fn"] = device_aug.collate

@@ -574,6 +574,30 @@ int hiast_aug2_colour_u8(const int64_t* ops, const int32_t* seg, const uint8_t* 
 int hiast_aug2_blur_u8(const int64_t* ops, const int32_t* seg, const int32_t* tabs, uint8_t* img, float* tmp, int B,
                        int H, int W, hiast_stream_t stream);
 
+/* ---- K15c: level 3 of the device-side sample path (cfg.dataset.device_aug_level: 3) ------------------------------
+ * FDA (augmentations.fourier_domain_adaptation) as a plan op, in its sparse-DFT form: the output is the view plus the
+ * real part of the inverse DFT of the (2 border + 1)^2 centre bins whose amplitude the target replaces,
+ *   S = sum v exp(-2 pi i (ky y / H + kx x / W)),  D = (|T| - |S|) S / |S|  (phase 1 for S == 0),
+ *   out = trunc(clip(v + sum_bins Re(D exp(+2 pi i ...)) / (H W), 0, 255)),
+ * float64 throughout in a fixed order (device_aug.fda_u8 is the numpy restatement; bytes are equal except where the
+ * value before truncation is within 1e-6 of an integer).  One further op type of an ops row:
+ *   HIAST_AUG_OP_FDA       blob offset of the target view (uint8 [H][W][3], the reference image resized to the view)
+ *                          | border << HIAST_AUG_FDA_BORDER_SHIFT, border 0..HIAST_AUG_FDA_MAX_BORDER, min(H, W) >= 8
+ * An FDA op closes a segment as a blur does: its index stands in seg[b][3] and its launches follow the segment's
+ * colour pass (hiast_aug2_blur_u8 skips a sample whose closing op is no blur, hiast_aug3_fda_u8 one whose closing op
+ * is no FDA: its bytes are not touched).  Any number of FDA ops per row.
+ * hiast_aug3_fda_u8: in place on img uint8 [B][H][W][3].  trig: float64 cos[H], sin[H], cos[W], sin[W] of
+ *   2 pi j / n (built on the host).  ws: hiast_aug3_fda_workspace_bytes(B, H, W) bytes, 8-byte aligned.  Three launches:
+ *   per (sample, view | target, band of 32 rows) the partial bin sums (rows reduced along x, then times the row factors;
+ *   in the wave, then through LDS; no floating-point atomics), per sample the partials in band order and D / (H W),
+ *   then the pointwise apply. */
+#define HIAST_AUG_OP_FDA 8
+#define HIAST_AUG_FDA_MAX_BORDER 2
+#define HIAST_AUG_FDA_BORDER_SHIFT 40
+size_t hiast_aug3_fda_workspace_bytes(int B, int H, int W);
+int hiast_aug3_fda_u8(const int64_t* ops, const int32_t* seg, const uint8_t* blob, const double* trig, uint8_t* img,
+                      double* ws, int B, int H, int W, hiast_stream_t stream);
+
 /* K11b: copy n_tensors small tensors in one launch (the BatchNorm buffers update_ema_model copies from the student,
  * utils/utils.py:120-123).  table: device array of {dst, src, nbytes}; one block per tensor. */
 typedef struct { void* dst; const void* src; int64_t nbytes; } hiast_copy_rec;

@@ -5,7 +5,9 @@ processes -> H2D -> teacher forward, student forward/backward, Adam, EMA).  Prin
 next to the compute-only number bench.py reports.
     python tools/run_trainer_synth.py [N=32] [batch=8] [workers=14] [iters=24] [native_h=1024] [native_w=2048] [device_aug=0]
 device_aug=1: cfg.dataset.device_aug — the workers plan, the device crops / resamples / recolours (DESIGN §5);
-device_aug=2: the same at cfg.dataset.device_aug_level 2 (ColorJitter and GaussianBlur on the device too)."""
+device_aug=2: the same at cfg.dataset.device_aug_level 2 (ColorJitter and GaussianBlur on the device too);
+device_aug=3: level 3 (FDA on the device too; this tool's ['MS', 'CCA'] target list holds none — tools/bench_fda.py
+measures a ['MS', 'FDA-Target'] source set through the DataLoader at level 2 against level 3)."""
 import os
 import shutil
 import sys
@@ -38,7 +40,7 @@ iters = int(sys.argv[4]) if len(sys.argv) > 4 else 24
 nh = int(sys.argv[5]) if len(sys.argv) > 5 else 1024
 nwid = int(sys.argv[6]) if len(sys.argv) > 6 else 2048
 aug_level = int(sys.argv[7]) if len(sys.argv) > 7 else 0
-assert aug_level in (0, 1, 2), "device_aug is 0, 1 or 2"
+assert aug_level in (0, 1, 2, 3), "device_aug is 0, 1, 2 or 3"
 dev_aug = aug_level > 0
 root = tempfile.mkdtemp(prefix="hiast_train_")
 try:
