@@ -481,6 +481,7 @@ struct LossGeom {
 
 static int loss_geom(int h, int w, int H, int W, LossGeom* g)
 {
+    if (H < h || W < w) return HIAST_E_RANGE;   // the kernels upsample: hiast_st_loss_workspace_bytes is 0 for these too
     g->sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.0f;
     g->sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.0f;
     int TI = g->sw > 0.f ? (int)(253.0f * g->sw) : w;   // TI cells span <= TI/sw + 1 <= 254 columns

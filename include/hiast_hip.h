@@ -168,8 +168,16 @@ int hiast_plabel_pass1_tta(const float* const* z, const float* const* zf, const 
  * (0/0 = NaN, as in the reference).
  * region: 0 'ignored' (plbl==255), 1 'confident', 2 'all' (losses.py:77-82).
  * teacher_lr may be NULL (no consistency term; s3 = s6 = 0).
- * plbl: uint8 or int64 [B,H,W] (is_i64).
+ * plbl: uint8 or int64 [B,H,W] (is_i64).  A label outside [0, C) + {255} is NOT detected: it counts as confident (slot 4)
+ *   and matches no class (its -logp[y] is lse, its CE gradient p_c).
  * workspace: hiast_st_loss_workspace_bytes(...) bytes of scratch.
+ * Geometry: the entries upsample, H >= h and W >= w are required (HIAST_E_RANGE otherwise), B <= 65535 and h <= 65535 (grid
+ *   limits).  The backward gives every output column of a block of TI low-res cells one of its 256 threads, so each block
+ *   must stay within 256 columns: with sw = (w - 1) / (W - 1) in float32, TI = min(max(int(253 sw), 1), 253, w) and
+ *   TI / sw + 2 <= 256 (w = 1: W <= 256) — about W - 1 <= 254 (w - 1), the largest W for w = 1 .. 9 being 256, 255, 509, 763,
+ *   1017, 1271, 1525, 1779, 2033.  hiast_st_loss_workspace_bytes(...) == 0 IS the test: it returns 0 exactly for the
+ *   geometries both entries refuse with HIAST_E_RANGE (H < h and W < w among them), never for positive extents they accept.  Class counts
+ *   other than 19, 16, 9, 2 are HIAST_E_RANGE.  A refused call launches nothing and writes nothing.
  *
  * The consistency term is pluggable, as cfg.cst_training.cst_loss.type of the reference (losses.py:9-41): the
  * hiast_st_loss_cst_* entries take cst_kind; hiast_st_loss_fwd / _bwd are their cst_kind = 0 call.  With z the upsampled
@@ -199,7 +207,11 @@ int hiast_st_loss_fwd(const float* logits_lr, const float* teacher_lr, const voi
                       hiast_stream_t stream);
 /* d(Σ_i coef_i * loss_i)/d logits_lr, with the loss_i normalised as above.
  * coef f32 [4] (device) = grad_output_i * weight_i for (CE, KLD, ENT, CST).
- * dlogits_lr [B,C,h,w] is overwritten. */
+ * dlogits_lr [B,C,h,w] is overwritten.
+ * The factor of term i is A_i = (float)((double)coef_i / denominator_i), and exactly 0 when coef_i == 0 — so a loss whose
+ * denominator is 0 (no confident pixel: s4; no ignored pixel: s5; an empty region: s6) leaves the gradient finite as long as
+ * its coef is 0.  A zero denominator with a non-zero coef gives A_i = ±inf: every cell the term reaches is then NaN (0 · inf)
+ * or ±inf, as the reference's 0/0 loss would make it. */
 int hiast_st_loss_bwd(const float* logits_lr, const float* teacher_lr, const void* plbl,
                       int plbl_is_i64, int B, int C, int h, int w, int H, int W, int region,
                       const double* sums, const float* coef, float* dlogits_lr,
