@@ -35,7 +35,7 @@ int hiast_grid_cus();
 
 namespace hiast {
 
-// The class counts that the kernels with one register per class (st_loss, dinput) are instantiated for (host):
+// The class counts that the kernels with one register per class (st_loss, dinput, plabel*) are instantiated for (host):
 // calls f(std::integral_constant<int, C>{}); false, and no call, for any other C.
 template <class F>
 static inline bool for_class_count(int C, F&& f)

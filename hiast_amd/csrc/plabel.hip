@@ -6,26 +6,14 @@
 //         owns one output column X of one "band" (the 8-9 output rows that share a pair of
 //         low-res source rows), keeps the horizontally-lerped top/bottom row values of all C
 //         classes in registers (2*C VGPRs) and walks down the band.
-//         Histogram: wave-aggregated — lanes holding the same (class, bin) key elect a leader
-//         that issues ONE integer atomic of the popcount.
+//         Histogram: the counters of plabel_common.h (top bins in LDS, wave-aggregated adds,
+//         scattered workspace); this file defines the workspace's host side and its merge kernel.
 // pass 2: threshold select + per-image class counts + exact integer Σ prob.
-#include "common.h"
+#include "plabel_common.h"
 
 namespace hiast {
 
-// Scattered histogram layout of the pass-1 workspace.  On real maps a few classes and the confidences 0.5 .. 1 take nearly
-// all pixels: in the natural [class][bin] layout their ~2000 counters are ~60 lines of 128 B, and integer atomics on
-// one line execute one after the other at the memory side (tools/micro/int_atomics.hip: 3.1 M adds inside 60 lines 0.42 ms,
-// over >= 240 lines 0.12 ms = the chip's rate of 26 G atomics/s).  The workspace stores counter (class c, bin) at word
-// ((bin & 255) * C + c) * 61 + (bin >> 8): neighbouring bins are 256 planes apart, the hot counters lie on several hundred
-// lines.  hist_merge_kernel adds the workspace into the caller's [class][bin] histogram.
-constexpr int HIST_PLANE = (HIAST_NBINS + 255) / 256;                 // 61 words per (low byte, class)
-template <int C>
-__device__ __forceinline__ unsigned hist_slot(unsigned key)
-{
-    const unsigned c = key / HIAST_NBINS, bin = key - c * HIAST_NBINS;
-    return ((bin & 255u) * C + c) * HIST_PLANE + (bin >> 8);
-}
+// ---- the scattered counting workspace (layout: hist_slot of plabel_common.h) ------------------------------------------------
 template <int C>
 __global__ __launch_bounds__(256) void hist_merge_kernel(const uint32_t* __restrict__ ws, uint32_t* __restrict__ hist)
 {
@@ -34,13 +22,24 @@ __global__ __launch_bounds__(256) void hist_merge_kernel(const uint32_t* __restr
     const unsigned v = ws[hist_slot<C>(key)];
     if (v) hist[key] += v;                       // (one thread per counter; calls on one stream are ordered)
 }
+size_t hist_ws_bytes(int C) { return C > 0 && C <= HIAST_MAX_CLASSES ? (size_t)256 * C * HIST_PLANE * sizeof(uint32_t) : 0; }
+int hist_ws_clear(uint32_t* ws, int C, hipStream_t st) { return (int)hipMemsetAsync(ws, 0, hist_ws_bytes(C), st); }
+int hist_ws_merge(const uint32_t* ws, uint32_t* hist, int C, hipStream_t st)
+{
+    const bool known = for_class_count(C, [&](auto cc) {
+        constexpr int CC = decltype(cc)::value;
+        hipLaunchKernelGGL(hist_merge_kernel<CC>, dim3((CC * HIAST_NBINS + 255) / 256), dim3(256), 0, st, ws, hist);
+    });
+    if (!known) return HIAST_E_RANGE;
+    HIAST_CHECK_LAUNCH();
+    return 0;
+}
 
 // One work item of pass 1: 256 output columns (tile xt) of one band j of image b; thread t owns one column.
 // MODE 0: counts straight into hist [C][NBINS]; 1: into the scattered workspace; both count the top TOPB bins in LDS
 // (s_cnt = unsigned [C * TOPB], one block = one item).  MODE 2: all bins >= 0.5 (fp16 0x3800 .. 0x3C00) are counted in LDS
 // as packed 16-bit pairs (s_cnt = unsigned [C * UPW]) by a persistent block that works through many items before it
 // flushes; the rest goes to the scattered workspace.
-constexpr int TOPB = 128;
 constexpr int UPLO = 0x3800;                                          // fp16(0.5)
 constexpr int UPW = (HIAST_NBINS - UPLO + 1) / 2;                     // 513 words per class
 template <int C, int MODE>
@@ -84,7 +83,7 @@ __device__ __forceinline__ void pass1_item(const float* __restrict__ logits, int
         for (int c = 0; c < C; ++c) s = s + a_expf(z[c] - m);
         const float prob = 1.0f / s;                         // IEEE division
 
-        unsigned key = 0xFFFFFFFFu;
+        unsigned key = NOKEY;
         if (live) {
             const size_t o = ((size_t)b * H + Y) * W + X;
             maxprob[o] = prob;
@@ -96,27 +95,10 @@ __device__ __forceinline__ void pass1_item(const float* __restrict__ logits, int
                     atomicAdd(&s_cnt[am * UPW + (int)(i >> 1)], (i & 1u) ? 65536u : 1u);
                 } else if (bin < HIAST_NBINS) key = (unsigned)am * HIAST_NBINS + bin;
             } else {
-                if (bin >= HIAST_NBINS - TOPB && bin < HIAST_NBINS)
-                    atomicAdd(&s_cnt[am * TOPB + (int)(bin - (HIAST_NBINS - TOPB))], 1u);
-                else if (bin < HIAST_NBINS) key = (unsigned)am * HIAST_NBINS + bin;
+                key = top_count(s_cnt, am, bin);
             }
         }
-        // Histogram update of the keys not counted in LDS.  Two wave-aggregated rounds take out the keys many lanes share
-        // (flat regions: 64 same-address atomics would serialise), the lanes that are left add their own count: on
-        // realistic confidences nearly every lane of a wave holds a different (class, fp16 bin) key, and the fully
-        // aggregated loop then ran 64 ballot / shuffle rounds per wave row (1.85 ms per 8-image batch; the integer sums
-        // are the same in any order).
-        unsigned long long todo = __ballot(key != 0xFFFFFFFFu);
-#pragma unroll
-        for (int round = 0; round < 2; ++round) {
-            if (!todo) break;
-            const int leader = __ffsll((long long)todo) - 1;
-            const unsigned k = __shfl(key, leader, 64);
-            const unsigned long long same = __ballot(key == k);
-            if (lane_id() == leader) atomicAdd(&hist[MODE ? hist_slot<C>(k) : k], (unsigned)__popcll(same));
-            todo &= ~same;
-        }
-        if ((todo >> lane_id()) & 1ull) atomicAdd(&hist[MODE ? hist_slot<C>(key) : key], 1u);
+        wave_add<2, C, MODE != 0>(hist, key);               // the keys not counted in LDS
     }
 }
 
@@ -125,20 +107,13 @@ __global__ __launch_bounds__(256) void plabel_pass1_kernel(
     const float* __restrict__ logits, int h, int w, int H, int W, float sh, float sw,
     float* __restrict__ maxprob, uint8_t* __restrict__ argmax, uint32_t* __restrict__ hist)
 {
-    // The TOP fp16 bins (confidence >= 1 - 128 * 2^-11 ~ 0.94) of every class are counted in LDS first and flushed once
-    // per block: on confident predictions most pixels of the whole batch fall into a handful of (class, bin) counters
-    // (0.99 ms per 8-image batch with every lane adding to global memory).
     __shared__ unsigned s_top[C * TOPB];
-    for (int i = threadIdx.x; i < C * TOPB; i += 256) s_top[i] = 0u;
+    top_zero<C>(s_top);
     __syncthreads();
     pass1_item<C, SCATTER ? 1 : 0>(logits, h, w, H, W, sh, sw, maxprob, argmax, hist, s_top, blockIdx.z, blockIdx.y, blockIdx.x,
                                    threadIdx.x);
     __syncthreads();
-    for (int i = threadIdx.x; i < C * TOPB; i += 256) {
-        const unsigned v = s_top[i];
-        const unsigned k = (unsigned)(i / TOPB) * HIAST_NBINS + (HIAST_NBINS - TOPB) + (unsigned)(i % TOPB);
-        if (v) atomicAdd(&hist[SCATTER ? hist_slot<C>(k) : k], v);
-    }
+    top_flush<C, SCATTER>(s_top, hist);
 }
 
 // Persistent form (round 3): 1024 threads = four 256-column groups that share ONE LDS histogram of the bins >= 0.5 and work
@@ -195,28 +170,24 @@ static int launch_pass1(const float* logits, int B, int h, int w, int H, int W, 
     const int nx = (W + 255) / 256;
     const long long items = (long long)nx * h * B;
     const int chunk = 65535 / (4 * 256 * rows);
+    if (ws) {
+        const int e0 = hist_ws_clear(ws, C, st);
+        if (e0) return e0;
+    }
     if (ws && chunk >= 1 && items < (1ll << 30)) {
-        const hipError_t e0 = hipMemsetAsync(ws, 0, (size_t)256 * C * HIST_PLANE * sizeof(uint32_t), st);
-        if (e0 != hipSuccess) return (int)e0;
         const int cus = hiast_grid_cus();                 // persistent: one 1024-thread block per CU
         const int blocks = (int)(items / 4 < cus ? (items + 3) / 4 : cus);
         hipLaunchKernelGGL(plabel_pass1_persistent_kernel<C>, dim3(blocks), dim3(1024), 0, st, logits, h, w, H, W, sh, sw,
                            maxprob, argmax, ws, nx, (int)items, chunk);
-        HIAST_CHECK_LAUNCH();
-        hipLaunchKernelGGL(hist_merge_kernel<C>, dim3((C * HIAST_NBINS + 255) / 256), dim3(256), 0, st, ws, hist);
     } else if (ws) {
-        const hipError_t e0 = hipMemsetAsync(ws, 0, (size_t)256 * C * HIST_PLANE * sizeof(uint32_t), st);
-        if (e0 != hipSuccess) return (int)e0;
         hipLaunchKernelGGL((plabel_pass1_kernel<C, true>), grid, dim3(256), 0, st, logits, h, w, H, W, sh, sw, maxprob,
                            argmax, ws);
-        HIAST_CHECK_LAUNCH();
-        hipLaunchKernelGGL(hist_merge_kernel<C>, dim3((C * HIAST_NBINS + 255) / 256), dim3(256), 0, st, ws, hist);
     } else {
         hipLaunchKernelGGL((plabel_pass1_kernel<C, false>), grid, dim3(256), 0, st, logits, h, w, H, W, sh, sw, maxprob,
                            argmax, hist);
     }
     HIAST_CHECK_LAUNCH();
-    return 0;
+    return ws ? hist_ws_merge(ws, hist, C, st) : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -305,10 +276,7 @@ __global__ __launch_bounds__(256) void plabel_pass2_kernel(
 
 }  // namespace hiast
 
-extern "C" size_t hiast_plabel_pass1_workspace_bytes(int C)
-{
-    return C > 0 && C <= HIAST_MAX_CLASSES ? (size_t)256 * C * hiast::HIST_PLANE * sizeof(uint32_t) : 0;
-}
+extern "C" size_t hiast_plabel_pass1_workspace_bytes(int C) { return hiast::hist_ws_bytes(C); }
 
 extern "C" int hiast_plabel_pass1(const float* logits_lr, int B, int C, int h, int w, int H, int W,
                                   float* maxprob, uint8_t* argmax, uint32_t* hist, void* workspace,
@@ -320,13 +288,11 @@ extern "C" int hiast_plabel_pass1(const float* logits_lr, int B, int C, int h, i
     if (workspace && (workspace_bytes < hiast_plabel_pass1_workspace_bytes(C) || (((uintptr_t)workspace) & 3))) return HIAST_E_WS;
     hipStream_t st = (hipStream_t)stream;
     uint32_t* ws = (uint32_t*)workspace;
-    switch (C) {
-        case 19: return hiast::launch_pass1<19>(logits_lr, B, h, w, H, W, maxprob, argmax, hist, ws, st);
-        case 16: return hiast::launch_pass1<16>(logits_lr, B, h, w, H, W, maxprob, argmax, hist, ws, st);
-        case 9: return hiast::launch_pass1<9>(logits_lr, B, h, w, H, W, maxprob, argmax, hist, ws, st);
-        case 2: return hiast::launch_pass1<2>(logits_lr, B, h, w, H, W, maxprob, argmax, hist, ws, st);
-        default: return HIAST_E_RANGE;   // class counts of the reference's datasets (19 / 9) + tests
-    }
+    int rc = HIAST_E_RANGE;              // class counts of the reference's datasets (19 / 9) + tests
+    hiast::for_class_count(C, [&](auto cc) {
+        rc = hiast::launch_pass1<decltype(cc)::value>(logits_lr, B, h, w, H, W, maxprob, argmax, hist, ws, st);
+    });
+    return rc;
 }
 
 extern "C" int hiast_plabel_pass2(const float* maxprob, const uint8_t* argmax, const float* thr_up,

@@ -143,14 +143,26 @@ def upsample_bilinear_ac_bwd(gout, h, w):
 
 
 # ------------------------------------------------------------------------------- K3/K4 pseudo labels
-_pass1_ws = {}
+_scatter_ws = {}
 
 
-def plabel_pass1(logits_lr, H, W, hist=None):
-    """-> (maxprob f32 [B,H,W], argmax u8 [B,H,W], hist u32-as-int32 [C,NBINS] (accumulated))"""
-    _req(logits_lr, torch.float32, 4, "logits_lr")
-    B, C, h, w = logits_lr.shape
-    dev = logits_lr.device
+def _scatter_workspace(t, C):
+    """the scattered counting copy of the histogram (hot counters on different memory lines) that pass 1 and pass 1 over views
+    count into: one per device, stream and class count, zeroed by the call; a second launch adds it into hist.  Keyed by the
+    device INDEX of tensor t — torch.device("cuda") and ("cuda", 0) are different keys — and the stream handle; the table holds
+    at most a few streams per device, so a recycled handle at worst reuses a buffer of the right size."""
+    key = (t.get_device(), torch.cuda.current_stream(t.device).cuda_stream, C)
+    ws = _scatter_ws.get(key)
+    if len(_scatter_ws) > 16 and ws is None:
+        _scatter_ws.clear()
+    if ws is None:
+        ws = torch.empty(_lib.load().hiast_plabel_pass1_workspace_bytes(C) // 4, dtype=torch.int32, device=t.device)
+        _scatter_ws[key] = ws
+    return ws
+
+
+def _pass1_outputs(B, C, H, W, hist, dev):
+    """-> (maxprob, argmax, hist) of pass 1; a given hist is checked, not zeroed"""
     maxprob = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     argmax = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     if hist is None:
@@ -158,21 +170,18 @@ def plabel_pass1(logits_lr, H, W, hist=None):
     else:
         _req(hist, torch.int32, 2, "hist")
         assert tuple(hist.shape) == (C, NBINS)
+    return maxprob, argmax, hist
+
+
+def plabel_pass1(logits_lr, H, W, hist=None):
+    """-> (maxprob f32 [B,H,W], argmax u8 [B,H,W], hist u32-as-int32 [C,NBINS] (accumulated))"""
+    _req(logits_lr, torch.float32, 4, "logits_lr")
+    B, C, h, w = logits_lr.shape
+    maxprob, argmax, hist = _pass1_outputs(B, C, H, W, hist, logits_lr.device)
     if B:
-        lib = _lib.load()
-        # scattered counting copy of the histogram (hot counters on different memory lines): one per device and stream,
-        # zeroed by the call; a second launch adds it into hist
-        # (keyed by the device INDEX — torch.device("cuda") and ("cuda", 0) are different keys — and the stream handle; the
-        # table holds at most a few streams per device, so a recycled handle at worst reuses a buffer of the right size)
-        key = (logits_lr.get_device(), torch.cuda.current_stream(dev).cuda_stream, C)
-        ws = _pass1_ws.get(key)
-        if len(_pass1_ws) > 16 and ws is None:
-            _pass1_ws.clear()
-        if ws is None:
-            ws = torch.empty(lib.hiast_plabel_pass1_workspace_bytes(C) // 4, dtype=torch.int32, device=dev)
-            _pass1_ws[key] = ws
-        check(lib.hiast_plabel_pass1(_ptr(logits_lr), B, C, h, w, H, W, _ptr(maxprob), _ptr(argmax), _ptr(hist), _ptr(ws),
-                                     ws.numel() * 4, _stream()), "hiast_plabel_pass1")
+        ws = _scatter_workspace(logits_lr, C)
+        check(_lib.load().hiast_plabel_pass1(_ptr(logits_lr), B, C, h, w, H, W, _ptr(maxprob), _ptr(argmax), _ptr(hist), _ptr(ws),
+                                             ws.numel() * 4, _stream()), "hiast_plabel_pass1")
     return maxprob, argmax, hist
 
 
@@ -243,10 +252,8 @@ def tta_fused_supported(C, n_scales):
     return int(C) in TTA_FUSED_CLASSES and 1 <= int(n_scales) <= TTA_FUSED_MAX_SCALES
 
 
-def tta_fused(zs, zfs, sizes, H, W, want_probs=False, want_label=True):
-    """Validator.get_multi_scale_and_flip_logits (+ argmax) from the low-res head outputs of every (scale, flip)
-    forward: zs / zfs lists of fp32 [B,C,hs,ws] (zfs None = no flip), sizes list of (Hs, Ws) the image was resized to
-    -> (probsum fp32 [B,C,H,W] or None, label u8 [B,H,W] or None)"""
+def _view_args(zs, zfs, sizes):
+    """the checked view lists of tta_fused / plabel_pass1_tta -> (n, B, C, the C ABI's host arrays (z, zf, hs, ws, Hs, Ws))"""
     n = len(zs)
     assert n == len(sizes) and n > 0
     B, C = zs[0].shape[:2]
@@ -258,23 +265,25 @@ def tta_fused(zs, zfs, sizes, H, W, want_probs=False, want_label=True):
         for z, zf in zip(zs, zfs):
             _req(zf, torch.float32, 4, "zf")
             assert zf.shape == z.shape
-    dev = zs[0].device
     vp = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
     iv = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    return n, B, C, (vp(zs), vp(zfs) if zfs is not None else None, iv([z.shape[2] for z in zs]), iv([z.shape[3] for z in zs]),
+                     iv([s[0] for s in sizes]), iv([s[1] for s in sizes]))
+
+
+def tta_fused(zs, zfs, sizes, H, W, want_probs=False, want_label=True):
+    """Validator.get_multi_scale_and_flip_logits (+ argmax) from the low-res head outputs of every (scale, flip)
+    forward: zs / zfs lists of fp32 [B,C,hs,ws] (zfs None = no flip), sizes list of (Hs, Ws) the image was resized to
+    -> (probsum fp32 [B,C,H,W] or None, label u8 [B,H,W] or None)"""
+    n, B, C, views = _view_args(zs, zfs, sizes)
+    dev = zs[0].device
     probs = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if want_probs else None
     label = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if want_label else None
-    check(_lib.load().hiast_tta_fused(vp(zs), vp(zfs) if zfs is not None else None, iv([z.shape[2] for z in zs]),
-                                      iv([z.shape[3] for z in zs]), iv([s[0] for s in sizes]), iv([s[1] for s in sizes]),
-                                      n, B, C, int(H), int(W), _ptr(probs), _ptr(label), _stream()), "hiast_tta_fused")
+    check(_lib.load().hiast_tta_fused(*views, n, B, C, int(H), int(W), _ptr(probs), _ptr(label), _stream()), "hiast_tta_fused")
     return probs, label
 
 
-_pass1_tta_ws = {}
-
-
-def plabel_pass1_tta_supported(C, n_scales):
-    """whether hiast_plabel_pass1_tta covers this class count / number of scales (it returns HIAST_E_RANGE otherwise)"""
-    return int(C) in TTA_FUSED_CLASSES and 1 <= int(n_scales) <= TTA_FUSED_MAX_SCALES
+plabel_pass1_tta_supported = tta_fused_supported          # hiast_plabel_pass1_tta covers what hiast_tta_fused covers
 
 
 def plabel_pass1_tta(zs, zfs, sizes, H, W, hist=None):
@@ -282,45 +291,16 @@ def plabel_pass1_tta(zs, zfs, sizes, H, W, hist=None):
     resized images / their mirror images (zfs None = no flip), sizes list of (Hs, Ws) the image was resized to
     -> (maxprob f32 [B,H,W] = mean probability of the label over the views, argmax u8 [B,H,W] = the validator's label,
     hist u32-as-int32 [C,NBINS] (accumulated))"""
-    n = len(zs)
-    assert n == len(sizes) and n > 0
-    B, C = zs[0].shape[:2]
-    for z in zs:
-        _req(z, torch.float32, 4, "z")
-        assert tuple(z.shape[:2]) == (B, C)
-    if zfs is not None:
-        assert len(zfs) == n
-        for z, zf in zip(zs, zfs):
-            _req(zf, torch.float32, 4, "zf")
-            assert zf.shape == z.shape
+    n, B, C, views = _view_args(zs, zfs, sizes)
     H, W = int(H), int(W)
-    dev = zs[0].device
-    maxprob = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    argmax = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-    if hist is None:
-        hist = torch.zeros((C, NBINS), dtype=torch.int32, device=dev)
-    else:
-        _req(hist, torch.int32, 2, "hist")
-        assert tuple(hist.shape) == (C, NBINS)
+    maxprob, argmax, hist = _pass1_outputs(B, C, H, W, hist, zs[0].device)
     if B:
-        lib = _lib.load()
         if not plabel_pass1_tta_supported(C, n):
             raise _lib.HiastLibraryError("hiast_plabel_pass1_tta: %d classes / %d scales are outside what the kernel is built "
                                          "for (classes %s, at most %d scales)" % (C, n, TTA_FUSED_CLASSES, TTA_FUSED_MAX_SCALES))
-        # the scattered counting copy of the histogram: one per device, stream and class count, as plabel_pass1 keeps it
-        key = (zs[0].get_device(), torch.cuda.current_stream(dev).cuda_stream, C)
-        ws = _pass1_tta_ws.get(key)
-        if len(_pass1_tta_ws) > 16 and ws is None:
-            _pass1_tta_ws.clear()
-        if ws is None:
-            ws = torch.empty(lib.hiast_plabel_pass1_tta_workspace_bytes(C) // 4, dtype=torch.int32, device=dev)
-            _pass1_tta_ws[key] = ws
-        vp = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-        iv = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
-        check(lib.hiast_plabel_pass1_tta(vp(zs), vp(zfs) if zfs is not None else None, iv([z.shape[2] for z in zs]),
-                                         iv([z.shape[3] for z in zs]), iv([s[0] for s in sizes]), iv([s[1] for s in sizes]),
-                                         n, B, C, H, W, _ptr(maxprob), _ptr(argmax), _ptr(hist), _ptr(ws), ws.numel() * 4,
-                                         _stream()), "hiast_plabel_pass1_tta")
+        ws = _scatter_workspace(zs[0], C)
+        check(_lib.load().hiast_plabel_pass1_tta(*views, n, B, C, H, W, _ptr(maxprob), _ptr(argmax), _ptr(hist), _ptr(ws),
+                                                 ws.numel() * 4, _stream()), "hiast_plabel_pass1_tta")
     return maxprob, argmax, hist
 
 

@@ -129,8 +129,8 @@ int hiast_plabel_strided_hist(const float* maxprob, const uint8_t* argmax, int64
 /* ---- K16: multi-scale + flip test-time augmentation, fused tail -------------------------
  * Validator.get_multi_scale_and_flip_logits + argmax, workflows/validator.py:34-55,92, from the LOW-RES head outputs:
  *   out = sum_s interp( softmax(interp(z[s] -> Hs[s] x Ws[s])) + flip_w(softmax(interp(zf[s] -> ...))) -> H x W )
- * z, zf: HOST arrays of n_scales device pointers to [B,C,hs[s],ws[s]] fp32 (zf NULL or zf[s] NULL = no flip);
- * hs, ws, Hs, Ws: host int arrays.  probsum f32 [B,C,H,W] and/or label u8 [B,H,W] (either may be NULL):
+ * z, zf: HOST arrays of n_scales device pointers to [B,C,hs[s],ws[s]] fp32 (zf NULL = no flip; a zf with a NULL
+ * entry is HIAST_E_ARG); hs, ws, Hs, Ws: host int arrays.  probsum f32 [B,C,H,W] and/or label u8 [B,H,W] (either may be NULL):
  * neither full-resolution logits nor per-scale probability maps are stored. */
 #define HIAST_TTA_MAX_SCALES 8
 int hiast_tta_fused(const float* const* z, const float* const* zf, const int* hs, const int* ws, const int* Hs,

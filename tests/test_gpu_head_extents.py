@@ -7,8 +7,8 @@ workspaces start as 0xFF.  After each launch:
      instead; the accumulating outputs hist / count / sumprob_fx start from values the test chooses and are compared exactly;
      class_total, which the entry overwrites, starts from such a value too);
   3. ASPP outputs (both forms) and the upsample adjoint are inside the bound of head_ref.py at EVERY element; integer and byte
-     outputs are bit-equal to numpy / the C oracle; upsample forward, pass 1's maxprob and the TTA probability sums, which have
-     their oracle tests through the wrappers, are bit-equal to the wrapper (item 4);
+     outputs are bit-equal to numpy / the C oracle, and so are the TTA probability sums; upsample forward and pass 1's maxprob,
+     which have their oracle tests through the wrappers, are bit-equal to the wrapper (item 4);
   4. the payload is bit-equal to what the ordinary K.* wrapper returns for the same operands;
   5. a second launch gives the same bits; accumulating outputs double exactly;
   6. workspaces are carved at exactly the size the *_workspace_bytes entry returns.
@@ -510,12 +510,13 @@ def test_tta(K, lib, C, n, flip):
     lows = [((Hs - 1) // 8 + 1, (Ws - 1) // 8 + 1) for Hs, Ws in sizes]
     zs = [synth.logits_lr(1600 + 10 * i + C, B, C, hs, ws_, 3.0) for i, (hs, ws_) in enumerate(lows)]
     zfs = [synth.logits_lr(1650 + 10 * i + C, B, C, hs, ws_, 3.0) for i, (hs, ws_) in enumerate(lows)] if flip else None
-    _, label_o = cref.tta(zs, zfs, sizes, H, W, want_probs=False)
+    probs_o, label_o = cref.tta(zs, zfs, sizes, H, W, want_probs=True)
     inb = Bufs()
     Z = [inb.inp("z%d" % i, dev(z), BAND) for i, z in enumerate(zs)]
     ZF = [inb.inp("zf%d" % i, dev(z), BAND) for i, z in enumerate(zfs)] if flip else None
     wprobs, wlabel = K.tta_fused([dev(z) for z in zs], [dev(z) for z in zfs] if flip else None, sizes, H, W, want_probs=True)
     assert torch.equal(wlabel.cpu(), torch.from_numpy(label_o))
+    assert _biteq(wprobs, dev(probs_o)), "probsum is not the oracle's sum bit for bit"
     for want_p, want_l in ((True, False), (False, True), (True, True)):
         def run():
             b = Bufs()

@@ -1,6 +1,6 @@
 """Host side of the multi-view pseudo-label pass 1 (hiast_plabel_pass1_tta; no GPU): the workspace size, every refusal of the
-entry (made before any launch, so placeholder addresses are never dereferenced), the config key and the view-list logic of
-HipPlabelEngine."""
+entry (made before any launch, so placeholder addresses are never dereferenced) with the refusals of the view arguments repeated on
+hiast_tta_fused, which checks them with the same function, the config key and the view-list logic of HipPlabelEngine."""
 import ctypes
 
 import pytest
@@ -18,16 +18,18 @@ def lib():
     return _lib.load()
 
 
-def call(lib, **over):
-    """the entry on placeholder addresses; `over` replaces arguments (z / zf: lists of addresses or None; hs, ws, Hs, Ws: lists)"""
+def call(lib, fused=False, **over):
+    """hiast_plabel_pass1_tta (fused: hiast_tta_fused, which takes the same view arguments) on placeholder addresses; `over`
+    replaces arguments (z / zf: lists of addresses or None; hs, ws, Hs, Ws: lists)"""
     a = dict(z=[FAKE, FAKE], zf=[FAKE, FAKE], hs=[5, 7], ws=[9, 13], Hs=[33, 49], Ws=[65, 97], n_scales=2, B=2, C=19, H=33, W=65,
-             maxprob=FAKE, argmax=FAKE, hist=FAKE, workspace=None, workspace_bytes=0, stream=None)
+             maxprob=FAKE, argmax=FAKE, hist=FAKE, workspace=None, workspace_bytes=0, probsum=FAKE, label=FAKE, stream=None)
     a.update(over)
     vp = lambda v: None if v is None else (ctypes.c_void_p * len(v))(*v)
     iv = lambda v: None if v is None else (ctypes.c_int * len(v))(*v)
-    return lib.hiast_plabel_pass1_tta(vp(a["z"]), vp(a["zf"]), iv(a["hs"]), iv(a["ws"]), iv(a["Hs"]), iv(a["Ws"]), a["n_scales"],
-                                      a["B"], a["C"], a["H"], a["W"], a["maxprob"], a["argmax"], a["hist"], a["workspace"],
-                                      a["workspace_bytes"], a["stream"])
+    views = (vp(a["z"]), vp(a["zf"]), iv(a["hs"]), iv(a["ws"]), iv(a["Hs"]), iv(a["Ws"]), a["n_scales"], a["B"], a["C"], a["H"], a["W"])
+    if fused:
+        return lib.hiast_tta_fused(*views, a["probsum"], a["label"], a["stream"])
+    return lib.hiast_plabel_pass1_tta(*views, a["maxprob"], a["argmax"], a["hist"], a["workspace"], a["workspace_bytes"], a["stream"])
 
 
 def test_workspace_bytes(lib):
@@ -37,10 +39,9 @@ def test_workspace_bytes(lib):
         assert lib.hiast_plabel_pass1_tta_workspace_bytes(C) == 0
 
 
-REFUSED = [
+VIEWS_REFUSED = [                                 # the view arguments: one check for both entries
     ("z null", dict(z=None), E_ARG), ("hs null", dict(hs=None), E_ARG), ("ws null", dict(ws=None), E_ARG),
-    ("Hs null", dict(Hs=None), E_ARG), ("Ws null", dict(Ws=None), E_ARG), ("maxprob null", dict(maxprob=None), E_ARG),
-    ("argmax null", dict(argmax=None), E_ARG), ("hist null", dict(hist=None), E_ARG),
+    ("Hs null", dict(Hs=None), E_ARG), ("Ws null", dict(Ws=None), E_ARG),
     ("no scales", dict(n_scales=0), E_ARG), ("B = 0", dict(B=0), E_ARG), ("C = 0", dict(C=0), E_ARG), ("H = 0", dict(H=0), E_ARG),
     ("W = -1", dict(W=-1), E_ARG), ("a null view", dict(z=[FAKE, None]), E_ARG),
     ("zf with a null entry", dict(zf=[FAKE, None]), E_ARG), ("zf with its first entry null", dict(zf=[None, FAKE]), E_ARG),
@@ -48,11 +49,15 @@ REFUSED = [
     ("Hs < hs", dict(Hs=[4, 49]), E_ARG), ("Ws < ws", dict(Ws=[65, 12]), E_ARG),
     ("9 scales", dict(n_scales=9, z=[FAKE] * 9, zf=None, hs=[5] * 9, ws=[9] * 9, Hs=[33] * 9, Ws=[65] * 9), E_RANGE),
     ("B = 65536", dict(B=65536), E_RANGE), ("H = 65536", dict(H=65536), E_RANGE),
+]
+REFUSED = VIEWS_REFUSED + [
+    ("maxprob null", dict(maxprob=None), E_ARG), ("argmax null", dict(argmax=None), E_ARG), ("hist null", dict(hist=None), E_ARG),
     ("C = 5", dict(C=5), E_RANGE), ("C = 20", dict(C=20), E_RANGE), ("C = 18", dict(C=18), E_RANGE),
     ("workspace one byte short", dict(workspace=FAKE, workspace_bytes=256 * 19 * 61 * 4 - 1), E_WS),
     ("workspace of another class count", dict(workspace=FAKE, workspace_bytes=256 * 16 * 61 * 4), E_WS),
     ("workspace not 4-byte aligned", dict(workspace=FAKE + 2, workspace_bytes=256 * 19 * 61 * 4), E_WS),
 ]
+FUSED_REFUSED = VIEWS_REFUSED + [("both outputs null", dict(probsum=None, label=None), E_ARG), ("C = 5", dict(C=5), E_RANGE)]
 
 
 @pytest.mark.parametrize("what,change,code", REFUSED, ids=[r[0] for r in REFUSED])
@@ -60,6 +65,17 @@ def test_refusals_before_any_launch(lib, what, change, code):
     assert call(lib, **change) == code, what
     if "zf" not in change:
         assert call(lib, zf=None, **change) == code, what + " (no mirror views)"
+
+
+@pytest.mark.parametrize("what,change,code", FUSED_REFUSED, ids=[r[0] for r in FUSED_REFUSED])
+def test_tta_fused_refuses_the_same_views(lib, what, change, code):
+    """hiast_tta_fused on the same placeholder addresses: the same codes, with either output alone as well"""
+    assert call(lib, fused=True, **change) == code, what
+    if "zf" not in change:
+        assert call(lib, fused=True, zf=None, **change) == code, what + " (no mirror views)"
+    if "label" not in change:
+        assert call(lib, fused=True, label=None, **change) == code, what + " (probsum only)"
+        assert call(lib, fused=True, probsum=None, **change) == code, what + " (label only)"
 
 
 def test_wrapper_names_what_is_supported():
