@@ -100,8 +100,6 @@ SIGNATURES = {
     "hiast_maxpool3x3s2_nhwc_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "hiast_multi_copy": (c_int, [c_vp, c_int, c_vp]),
     "hiast_aug_geometry_u8": (c_int, [c_vp] * 6 + [c_int] * 4 + [c_vp]),
-    "hiast_aug_hist_u8": (c_int, [c_vp] * 5 + [c_int, c_i64, c_vp]),
-    "hiast_aug_colour_u8": (c_int, [c_vp] * 5 + [c_int, c_i64, c_vp]),
     "hiast_aug2_table_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
     "hiast_aug2_colour_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
     "hiast_aug2_blur_u8": (c_int, [c_vp] * 5 + [c_int] * 3 + [c_vp]),

@@ -1,26 +1,23 @@
 // K15 — the per-sample data path on the device (reference: sseg/datasets/augmentations.py + preprocessor.py, executed in
 // DataLoader workers through albumentations / OpenCV; here hiast_amd/sseg/datasets/augmentations.py is the host form).
 // A worker hands over bytes + a PLAN (hiast_amd/sseg/datasets/device_aug.py): every random decision is drawn on the
-// host, the kernels below are pure functions of bytes + plan and reproduce the host code BYTE FOR BYTE:
-//   geometry  CopyPaste select on load, flipped read, Pillow's two-pass 8-bit bilinear resample (22-bit fixed-point
-//             weights, the horizontal pass rounded to uint8 before the vertical one), nearest gather of the label
-//   colour    256-entry LUTs, OpenCV's fixed-point gray, cv2.equalizeHist (histogram -> float64 LUT, round half even)
+// host, the kernels are pure functions of bytes + plan and reproduce the host code BYTE FOR BYTE.  This file is the
+// geometry: CopyPaste select on load, flipped read, Pillow's two-pass 8-bit bilinear resample (22-bit fixed-point
+// weights, the horizontal pass rounded to uint8 before the vertical one), nearest gather of the label, all in integers.
+// The colour ops of every level (256-entry LUTs, OpenCV's fixed-point gray, cv2.equalizeHist, ...) are sample_aug2.hip.
 // One launch covers the whole batch: per sample one int64 record row of offsets into ONE uint8 blob and ONE int32 table
-// blob (hiast_hip.h), as hiast_ema_update / hiast_multi_copy do with pointers.  Everything is integer arithmetic except
-// the equalize scale (float64, one rounding per operation; the library is built with -ffp-contract=off).
+// blob (hiast_hip.h), as hiast_ema_update / hiast_multi_copy do with pointers.
 // Table indices are clamped to the sample's extent before they address memory: the host wrapper rejects a table that
 // points outside, the clamp keeps a wrong table from leaving the buffers.
-#include "common.h"
+#include "aug_common.h"
 
 namespace hiast {
 
 enum { R_KIND, R_IMG, R_LBL, R_PIMG, R_PLBL, R_PTAB, R_CH, R_CW, R_FLIP, R_HLO, R_HN, R_HK, R_HT, R_VLO, R_VN, R_VK, R_VT,
        R_NX, R_NY };
 constexpr int REC = HIAST_AUG_REC_WORDS;
-constexpr int OPS = HIAST_AUG_OPS_WORDS;
 constexpr int PBITS = 22;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ unsigned clip8(int v) { return (unsigned)clampi(v >> PBITS, 0, 255); }
 
 // horizontal pass: one thread per (output column, source row) of a planned sample -> tmp [B][max_ch][ow][3]
@@ -126,137 +123,6 @@ __global__ __launch_bounds__(256) void aug_vpass_kernel(const int64_t* __restric
     }
 }
 
-// ops [from, to) of one view's op row on one pixel; eq: the sample's [3][256] equalize tables
-__device__ __forceinline__ void aug_apply_ops(const int64_t* __restrict__ o, int from, int to, const uint8_t* __restrict__ blob,
-                                              const uint8_t* __restrict__ eq, unsigned& r, unsigned& g, unsigned& b)
-{
-    for (int i = from; i < to; ++i) {
-        const int type = (int)o[4 + 2 * i];
-        if (type == HIAST_AUG_OP_LUT) {
-            const uint8_t* lut = blob + o[5 + 2 * i];
-            r = lut[r];
-            g = lut[g];
-            b = lut[b];
-        } else if (type == HIAST_AUG_OP_GRAY) {
-            r = g = b = (r * 4899u + g * 9617u + b * 1868u + 8192u) >> 14;
-        } else if (type == HIAST_AUG_OP_EQUALIZE) {
-            r = eq[r];
-            g = eq[256 + g];
-            b = eq[512 + b];
-        }
-    }
-}
-
-__device__ __forceinline__ int aug_equalize_pos(const int64_t* o, int nops)
-{
-    for (int i = 0; i < nops; ++i)
-        if (o[4 + 2 * i] == HIAST_AUG_OP_EQUALIZE) return i;
-    return -1;
-}
-
-// per sample, per channel 256-bin histogram of the image an Equalize meets (the view's input after the ops before it):
-// LDS integer atomics, then one global integer atomic per non-empty bin
-__global__ __launch_bounds__(256) void aug_hist_kernel(const int64_t* __restrict__ ops, const uint8_t* __restrict__ blob,
-                                                       const uint8_t* __restrict__ in, unsigned* __restrict__ hist, long long HW)
-{
-    const int b = blockIdx.y;
-    const int64_t* o = ops + (size_t)b * OPS;
-    if (o[0] != 0) return;
-    const int nops = clampi((int)o[2], 0, HIAST_AUG_MAX_OPS);
-    const int e = aug_equalize_pos(o, nops);
-    if (e < 0) return;
-    __shared__ unsigned s_h[768];
-    for (int i = threadIdx.x; i < 768; i += 256) s_h[i] = 0;
-    __syncthreads();
-    const uint8_t* src = in + (size_t)b * HW * 3;
-    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
-        unsigned r = src[p * 3], g = src[p * 3 + 1], bl = src[p * 3 + 2];
-        aug_apply_ops(o, 0, e, blob, nullptr, r, g, bl);
-        atomicAdd(&s_h[r], 1u);
-        atomicAdd(&s_h[256 + g], 1u);
-        atomicAdd(&s_h[512 + bl], 1u);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 768; i += 256)
-        if (s_h[i]) atomicAdd(&hist[(size_t)b * 768 + i], s_h[i]);
-}
-
-// cv2.equalizeHist's table from a histogram: one thread per (sample, channel); float64, rint = round half to even
-__global__ __launch_bounds__(64) void aug_eq_lut_kernel(const unsigned* __restrict__ hist, uint8_t* __restrict__ eq, long long HW)
-{
-    if (threadIdx.x >= 3) return;
-    const unsigned* h = hist + (size_t)blockIdx.x * 768 + threadIdx.x * 256;
-    uint8_t* lut = eq + (size_t)blockIdx.x * 768 + threadIdx.x * 256;
-    int first = 0;
-    while (first < 256 && h[first] == 0) ++first;
-    if (first == 256) return;                              // no Equalize in this sample's list: the table is not read
-    if ((long long)h[first] == HW) {                       // constant channel: the image unchanged
-        for (int i = 0; i < 256; ++i) lut[i] = (uint8_t)first;
-        return;
-    }
-    const double scale = 255.0 / (double)(HW - (long long)h[first]);
-    long long s = 0;
-    for (int i = 0; i < 256; ++i) {
-        if (i <= first) {
-            lut[i] = 0;
-            continue;
-        }
-        s += h[i];
-        const double v = rint((double)s * scale);
-        lut[i] = (uint8_t)(v < 0.0 ? 0 : (v > 255.0 ? 255 : (int)v));
-    }
-}
-
-// a view's whole op list on uint8 HWC (or the copy of a finished view); 4 pixels = three 32-bit words per thread and step
-// when the sample's bytes allow it
-__global__ __launch_bounds__(256) void aug_colour_kernel(const int64_t* __restrict__ ops, const uint8_t* __restrict__ blob,
-                                                         const uint8_t* __restrict__ eq, const uint8_t* __restrict__ in,
-                                                         uint8_t* __restrict__ out, long long HW)
-{
-    const int b = blockIdx.y;
-    const int64_t* o = ops + (size_t)b * OPS;
-    const bool finished = o[0] != 0;
-    const int nops = finished ? 0 : clampi((int)o[2], 0, HIAST_AUG_MAX_OPS);
-    const uint8_t* src = finished ? blob + o[1] : in + (size_t)b * HW * 3;
-    uint8_t* dst = out + (size_t)b * HW * 3;
-    const uint8_t* e = eq + (size_t)b * 768;
-    const long long step = (long long)gridDim.x * 256;
-    if ((HW & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 3) == 0) {
-        const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src);
-        uint32_t* d4 = reinterpret_cast<uint32_t*>(dst);
-        for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < HW / 4; q += step) {
-            const uint32_t w0 = s4[q * 3], w1 = s4[q * 3 + 1], w2 = s4[q * 3 + 2];
-            unsigned c[12];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                c[i] = (w0 >> (8 * i)) & 255u;
-                c[4 + i] = (w1 >> (8 * i)) & 255u;
-                c[8 + i] = (w2 >> (8 * i)) & 255u;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) aug_apply_ops(o, 0, nops, blob, e, c[3 * i], c[3 * i + 1], c[3 * i + 2]);
-            uint32_t v0 = 0, v1 = 0, v2 = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v0 |= c[i] << (8 * i);
-                v1 |= c[4 + i] << (8 * i);
-                v2 |= c[8 + i] << (8 * i);
-            }
-            d4[q * 3] = v0;
-            d4[q * 3 + 1] = v1;
-            d4[q * 3 + 2] = v2;
-        }
-    } else {
-        for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += step) {
-            unsigned r = src[p * 3], g = src[p * 3 + 1], bl = src[p * 3 + 2];
-            aug_apply_ops(o, 0, nops, blob, e, r, g, bl);
-            dst[p * 3] = (uint8_t)r;
-            dst[p * 3 + 1] = (uint8_t)g;
-            dst[p * 3 + 2] = (uint8_t)bl;
-        }
-    }
-}
-
 }  // namespace hiast
 
 extern "C" int hiast_aug_geometry_u8(const int64_t* recs, const uint8_t* blob, const int32_t* tabs, uint8_t* tmp,
@@ -276,39 +142,6 @@ extern "C" int hiast_aug_geometry_u8(const int64_t* recs, const uint8_t* blob, c
     else
         hipLaunchKernelGGL(hiast::aug_vpass_kernel<1>, dim3((rowb + 255) / 256, oh, B), dim3(256), 0, (hipStream_t)stream,
                            recs, blob, tabs, tmp, img_out, lbl_out, max_ch, oh, ow);
-    HIAST_CHECK_LAUNCH();
-    return 0;
-}
-
-static int aug_pixel_blocks(int64_t HW)
-{
-    const int64_t nb = (HW / 4 + 255) / 256;
-    return (int)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb));
-}
-
-extern "C" int hiast_aug_hist_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* in, uint32_t* hist, uint8_t* eq_lut,
-                                 int B, int64_t HW, hiast_stream_t stream)
-{
-    if (!ops || !blob || !in || !hist || !eq_lut) return HIAST_E_ARG;
-    if (B <= 0 || HW <= 0) return HIAST_E_ARG;
-    if (B > 65535 || HW >= (1ll << 31)) return HIAST_E_RANGE;            // 32-bit bins
-    if (hipMemsetAsync(hist, 0, (size_t)B * 768 * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) return HIAST_E_ARG;
-    hipLaunchKernelGGL(hiast::aug_hist_kernel, dim3(aug_pixel_blocks(HW), B), dim3(256), 0, (hipStream_t)stream, ops, blob, in,
-                       hist, (long long)HW);
-    HIAST_CHECK_LAUNCH();
-    hipLaunchKernelGGL(hiast::aug_eq_lut_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, hist, eq_lut, (long long)HW);
-    HIAST_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int hiast_aug_colour_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* eq_lut, const uint8_t* in,
-                                   uint8_t* out, int B, int64_t HW, hiast_stream_t stream)
-{
-    if (!ops || !blob || !eq_lut || !in || !out) return HIAST_E_ARG;
-    if (B <= 0 || HW <= 0) return HIAST_E_ARG;
-    if (B > 65535) return HIAST_E_RANGE;
-    hipLaunchKernelGGL(hiast::aug_colour_kernel, dim3(aug_pixel_blocks(HW), B), dim3(256), 0, (hipStream_t)stream, ops, blob,
-                       eq_lut, in, out, (long long)HW);
     HIAST_CHECK_LAUNCH();
     return 0;
 }

@@ -1,6 +1,10 @@
-// K15b — level 2 of the device-side sample path (cfg.dataset.device_aug_level: 2): ColorJitter and GaussianBlur as plan
-// ops, BYTE FOR BYTE what hiast_amd/sseg/datasets/augmentations.py computes on the host (device_aug.py holds the numpy
-// restatements the kernels are tested against):
+// K15b — the colour ops of the device-side sample path at every level, BYTE FOR BYTE what
+// hiast_amd/sseg/datasets/augmentations.py computes on the host (device_aug.py holds the numpy restatements the kernels
+// are tested against).  Level 1 (the default):
+//   LUT         the 256-entry table the host code builds (neighbours composed on the host)
+//   gray        OpenCV's fixed point
+//   Equalize    cv2.equalizeHist: per-channel histogram -> float64 table, rint (half to even)
+// Level 2 (cfg.dataset.device_aug_level: 2), ColorJitter and GaussianBlur as plan ops:
 //   contrast    a 256-entry table built on the device from the gray mean of the image AT THAT POINT of the chain (the
 //               gray histogram -> an exact integer sum -> float64 mean), float32 multiply + add, truncated
 //   saturation  c * f32(f) + gray * f32(1 - f), each operation rounded to float32, truncated
@@ -10,17 +14,14 @@
 // A view's op row (hiast_hip.h) is cut into SEGMENTS by the host: ops [from, to) are pointwise except for at most one
 // table op (Equalize / contrast) at index `stat`, whose table is built from the image after ops [from, stat); a blur at
 // index `blur` (== to) closes the segment.  seg int32 [B][4] = (from, to, stat | -1, blur | -1) per sample and launch
-// round; a sample with an empty segment is skipped by its record, as finished samples are.
+// round; a sample with an empty segment is skipped by its record, as finished samples are.  A row of level-1 ops is one
+// segment (0, n_ops, index of its Equalize | -1, -1): one round, the table launches only if some row equalises.
 // The float32 quotients go through a float64 division (53 >= 2 * 24 + 2 bits: the double rounding is innocuous), so
 // they are correctly rounded whatever the compiler's float32 division is.  Built with -ffp-contract=off.
-#include "common.h"
+#include "aug_common.h"
 
 namespace hiast {
 
-constexpr int OPS2 = HIAST_AUG_OPS_WORDS;
-enum { S_FROM, S_TO, S_STAT, S_BLUR };
-
-__device__ __forceinline__ int clamp2(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ unsigned trunc8(float v) { return (unsigned)(int)(v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v)); }
 __device__ __forceinline__ float div32(float a, float b) { return (float)((double)a / (double)b); }
 __device__ __forceinline__ unsigned gray8(unsigned r, unsigned g, unsigned b) { return (r * 4899u + g * 9617u + b * 1868u + 8192u) >> 14; }
@@ -43,8 +44,8 @@ __device__ __forceinline__ void hue_shift(unsigned& r, unsigned& g, unsigned& b,
     else h = (float)(4.0 + (double)gc - (double)rc);
     const double hd = (double)h / 6.0 + 1.0;                 // in [5/6, 11/6]: fmod(hd, 1.0) == hd - floor(hd), exact
     h = (float)(hd - floor(hd));
-    unsigned H = (unsigned)clamp2((int)((double)h * 255.0), 0, 255);
-    const unsigned S = (unsigned)clamp2((int)((double)s * 255.0), 0, 255), V = maxc;
+    unsigned H = (unsigned)clampi((int)((double)h * 255.0), 0, 255);
+    const unsigned S = (unsigned)clampi((int)((double)s * 255.0), 0, 255), V = maxc;
     H = (H + shift) & 255u;
     if (S == 0) {
         r = g = b = V;
@@ -73,8 +74,8 @@ __device__ __forceinline__ void aug2_apply_ops(const int64_t* __restrict__ o, in
                                                const uint8_t* __restrict__ tab, unsigned& r, unsigned& g, unsigned& b)
 {
     for (int i = from; i < to; ++i) {
-        const int type = (int)o[4 + 2 * i];
-        const int64_t par = o[5 + 2 * i];
+        const int type = (int)op_type(o, i);
+        const int64_t par = op_par(o, i);
         if (type == HIAST_AUG_OP_LUT) {
             const uint8_t* lut = blob + par;
             r = lut[r];
@@ -105,22 +106,6 @@ __device__ __forceinline__ void aug2_apply_ops(const int64_t* __restrict__ o, in
     }
 }
 
-struct Seg {
-    int from, to, stat, blur;
-    bool live;
-};
-__device__ __forceinline__ Seg seg_of(const int64_t* o, const int32_t* sg)
-{
-    Seg s;
-    const int n = o[0] != 0 ? 0 : clamp2((int)o[2], 0, HIAST_AUG_MAX_OPS);
-    s.from = clamp2(sg[S_FROM], 0, n);
-    s.to = clamp2(sg[S_TO], s.from, n);
-    s.stat = (sg[S_STAT] >= s.from && sg[S_STAT] < s.to) ? sg[S_STAT] : -1;
-    s.blur = (sg[S_BLUR] >= 0 && sg[S_BLUR] < n) ? sg[S_BLUR] : -1;
-    s.live = o[0] == 0;
-    return s;
-}
-
 // histogram of the image a segment's table op meets: per channel (Equalize) or of the gray value (contrast, bins
 // 0..255 of the sample's 768): LDS integer atomics, then one global integer atomic per non-empty bin
 __global__ __launch_bounds__(256) void aug2_hist_kernel(const int64_t* __restrict__ ops, const int32_t* __restrict__ seg,
@@ -128,10 +113,10 @@ __global__ __launch_bounds__(256) void aug2_hist_kernel(const int64_t* __restric
                                                         unsigned* __restrict__ hist, long long HW)
 {
     const int b = blockIdx.y;
-    const int64_t* o = ops + (size_t)b * OPS2;
+    const int64_t* o = ops + (size_t)b * OPS;
     const Seg s = seg_of(o, seg + b * 4);
     if (!s.live || s.stat < 0) return;
-    const bool contrast = o[4 + 2 * s.stat] == HIAST_AUG_OP_CONTRAST;
+    const bool contrast = op_type(o, s.stat) == HIAST_AUG_OP_CONTRAST;
     __shared__ unsigned s_h[768];
     for (int i = threadIdx.x; i < 768; i += 256) s_h[i] = 0;
     __syncthreads();
@@ -159,15 +144,15 @@ __global__ __launch_bounds__(64) void aug2_table_kernel(const int64_t* __restric
 {
     if (threadIdx.x >= 3) return;
     const int b = blockIdx.x;
-    const int64_t* o = ops + (size_t)b * OPS2;
+    const int64_t* o = ops + (size_t)b * OPS;
     const Seg s = seg_of(o, seg + b * 4);
     if (!s.live || s.stat < 0) return;
     uint8_t* lut = tab + (size_t)b * 768 + threadIdx.x * 256;
-    if (o[4 + 2 * s.stat] == HIAST_AUG_OP_CONTRAST) {
+    if (op_type(o, s.stat) == HIAST_AUG_OP_CONTRAST) {
         const unsigned* h = hist + (size_t)b * 768;
         long long sum = 0;
         for (int i = 0; i < 256; ++i) sum += (long long)i * (long long)h[i];
-        const double fd = __longlong_as_double(o[5 + 2 * s.stat]);
+        const double fd = __longlong_as_double(op_par(o, s.stat));
         const double mean = (double)sum / (double)HW;
         const float f = (float)fd, add = (float)(mean * (1.0 - fd));
         for (int i = 0; i < 256; ++i) {
@@ -206,7 +191,7 @@ __global__ __launch_bounds__(256) void aug2_colour_kernel(const int64_t* __restr
                                                           const uint8_t* in, uint8_t* out, long long HW)
 {
     const int b = blockIdx.y;
-    const int64_t* o = ops + (size_t)b * OPS2;
+    const int64_t* o = ops + (size_t)b * OPS;
     const Seg s = seg_of(o, seg + b * 4);
     const bool inplace = in == out;
     if (inplace && (!s.live || s.to <= s.from)) return;
@@ -218,26 +203,11 @@ __global__ __launch_bounds__(256) void aug2_colour_kernel(const int64_t* __restr
         const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src);
         uint32_t* d4 = reinterpret_cast<uint32_t*>(dst);
         for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < HW / 4; q += step) {
-            const uint32_t w0 = s4[q * 3], w1 = s4[q * 3 + 1], w2 = s4[q * 3 + 2];
             unsigned c[12];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                c[i] = (w0 >> (8 * i)) & 255u;
-                c[4 + i] = (w1 >> (8 * i)) & 255u;
-                c[8 + i] = (w2 >> (8 * i)) & 255u;
-            }
+            unpack12(s4 + q * 3, c);
 #pragma unroll
             for (int i = 0; i < 4; ++i) aug2_apply_ops(o, s.from, s.to, blob, t, c[3 * i], c[3 * i + 1], c[3 * i + 2]);
-            uint32_t v0 = 0, v1 = 0, v2 = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                v0 |= c[i] << (8 * i);
-                v1 |= c[4 + i] << (8 * i);
-                v2 |= c[8 + i] << (8 * i);
-            }
-            d4[q * 3] = v0;
-            d4[q * 3 + 1] = v1;
-            d4[q * 3 + 2] = v2;
+            pack12(c, d4 + q * 3);
         }
     } else {
         for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += step) {
@@ -258,17 +228,17 @@ __device__ __forceinline__ int mirror(int i, int n)
 {
     i = i < 0 ? -i : i;
     i = i >= n ? 2 * (n - 1) - i : i;
-    return clamp2(i, 0, n - 1);                              // (s < n, checked by the host: the clamp never acts)
+    return clampi(i, 0, n - 1);                              // (s < n, checked by the host: the clamp never acts)
 }
 
 // the blur of this sample's segment: half width (0 = none) and its weights as float64 in LDS; block-uniform
 __device__ __forceinline__ int blur_of(const int64_t* __restrict__ ops, const int32_t* __restrict__ seg,
                                        const int32_t* __restrict__ tabs, int b, int H, int W, double* s_w)
 {
-    const int64_t* o = ops + (size_t)b * OPS2;
+    const int64_t* o = ops + (size_t)b * OPS;
     const Seg sg = seg_of(o, seg + b * 4);
-    if (!sg.live || sg.blur < 0 || o[4 + 2 * sg.blur] != HIAST_AUG_OP_BLUR) return 0;
-    const int64_t par = o[5 + 2 * sg.blur];
+    if (!sg.live || sg.blur < 0 || op_type(o, sg.blur) != HIAST_AUG_OP_BLUR) return 0;
+    const int64_t par = op_par(o, sg.blur);
     const int ks = (int)(par >> 32), s = ks >> 1;
     if (ks < 3 || ks > MAX_K || !(ks & 1) || s >= H || s >= W) return 0;
     if ((int)threadIdx.x < ks) s_w[threadIdx.x] = (double)__int_as_float(tabs[(par & 0xffffffffll) + threadIdx.x]);
@@ -361,12 +331,6 @@ __global__ __launch_bounds__(256) void aug2_blur_cols_kernel(const int64_t* __re
 
 }  // namespace hiast
 
-static int aug2_pixel_blocks(int64_t HW)
-{
-    const int64_t nb = (HW / 4 + 255) / 256;
-    return (int)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb));
-}
-
 extern "C" int hiast_aug2_table_u8(const int64_t* ops, const int32_t* seg, const uint8_t* blob, const uint8_t* in,
                                    uint32_t* hist, uint8_t* table, int B, int64_t HW, hiast_stream_t stream)
 {
@@ -374,7 +338,7 @@ extern "C" int hiast_aug2_table_u8(const int64_t* ops, const int32_t* seg, const
     if (B <= 0 || HW <= 0) return HIAST_E_ARG;
     if (B > 65535 || HW >= (1ll << 31)) return HIAST_E_RANGE;            // 32-bit bins
     if (hipMemsetAsync(hist, 0, (size_t)B * 768 * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) return HIAST_E_ARG;
-    hipLaunchKernelGGL(hiast::aug2_hist_kernel, dim3(aug2_pixel_blocks(HW), B), dim3(256), 0, (hipStream_t)stream, ops, seg,
+    hipLaunchKernelGGL(hiast::aug2_hist_kernel, dim3(aug_pixel_blocks(HW), B), dim3(256), 0, (hipStream_t)stream, ops, seg,
                        blob, in, hist, (long long)HW);
     HIAST_CHECK_LAUNCH();
     hipLaunchKernelGGL(hiast::aug2_table_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, ops, seg, hist, table,
@@ -389,7 +353,7 @@ extern "C" int hiast_aug2_colour_u8(const int64_t* ops, const int32_t* seg, cons
     if (!ops || !seg || !blob || !table || !in || !out) return HIAST_E_ARG;
     if (B <= 0 || HW <= 0) return HIAST_E_ARG;
     if (B > 65535) return HIAST_E_RANGE;
-    hipLaunchKernelGGL(hiast::aug2_colour_kernel, dim3(aug2_pixel_blocks(HW), B), dim3(256), 0, (hipStream_t)stream, ops, seg,
+    hipLaunchKernelGGL(hiast::aug2_colour_kernel, dim3(aug_pixel_blocks(HW), B), dim3(256), 0, (hipStream_t)stream, ops, seg,
                        blob, table, in, out, (long long)HW);
     HIAST_CHECK_LAUNCH();
     return 0;

@@ -14,11 +14,10 @@
 // (trig = cos[H], sin[H], cos[W], sin[W] of 2 pi j / n), the angle reduced by integer mod first.
 // Everything is float64 in a fixed order: no floating-point atomics, the same call returns the same bytes.
 // A sample whose segment is not closed by an FDA op (seg[b][3], K15b) is skipped by all three launches.
-#include "common.h"
+#include "aug_common.h"
 
 namespace hiast {
 
-constexpr int OPS3 = HIAST_AUG_OPS_WORDS;
 constexpr int FDA_NC = 1 + 2 * HIAST_AUG_FDA_MAX_BORDER;      // entries of e(y) / r(x)
 constexpr int FDA_NG = 3 * FDA_NC * FDA_NC;                   // doubles of one G / C record: [3][NC][NC]
 constexpr int FDA_ROWS = 32;                                  // rows of one launch-1 block
@@ -27,12 +26,10 @@ constexpr long long FDA_OFF_MASK = (1ll << HIAST_AUG_FDA_BORDER_SHIFT) - 1;
 // the FDA op that closes this sample's segment: its border (-1: none) and the blob offset of its target view
 __device__ __forceinline__ int fda_of(const int64_t* __restrict__ ops, const int32_t* __restrict__ seg, int b, long long& off)
 {
-    const int64_t* o = ops + (size_t)b * OPS3;
-    if (o[0] != 0) return -1;
-    const long long n = o[2] < 0 ? 0 : (o[2] > HIAST_AUG_MAX_OPS ? HIAST_AUG_MAX_OPS : o[2]);
-    const int i = seg[b * 4 + 3];
-    if (i < 0 || i >= n || o[4 + 2 * i] != HIAST_AUG_OP_FDA) return -1;
-    const long long par = o[5 + 2 * i];
+    const int64_t* o = ops + (size_t)b * OPS;
+    const Seg s = seg_of(o, seg + b * 4);
+    if (!s.live || s.blur < 0 || op_type(o, s.blur) != HIAST_AUG_OP_FDA) return -1;
+    const long long par = op_par(o, s.blur);
     const long long border = par >> HIAST_AUG_FDA_BORDER_SHIFT;
     if (par < 0 || border > HIAST_AUG_FDA_MAX_BORDER) return -1;
     off = par & FDA_OFF_MASK;
@@ -43,14 +40,7 @@ __device__ __forceinline__ int fda_of(const int64_t* __restrict__ ops, const int
 __device__ __forceinline__ void load4(const uint8_t* __restrict__ row, bool words, int x0, int n, unsigned (&v)[12])
 {
     if (words && n == 4) {
-        const uint32_t* p = reinterpret_cast<const uint32_t*>(row + (size_t)x0 * 3);
-        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[i] = (w0 >> (8 * i)) & 255u;
-            v[4 + i] = (w1 >> (8 * i)) & 255u;
-            v[8 + i] = (w2 >> (8 * i)) & 255u;
-        }
+        unpack12(reinterpret_cast<const uint32_t*>(row + (size_t)x0 * 3), v);
     } else {
 #pragma unroll
         for (int i = 0; i < 12; ++i) v[i] = i < 3 * n ? row[(size_t)x0 * 3 + i] : 0u;
@@ -248,17 +238,7 @@ __device__ __forceinline__ void fda_apply_row(uint8_t* __restrict__ row, const d
             }
         }
         if (words && n == 4) {
-            uint32_t w0 = 0, w1 = 0, w2 = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                w0 |= v[i] << (8 * i);
-                w1 |= v[4 + i] << (8 * i);
-                w2 |= v[8 + i] << (8 * i);
-            }
-            uint32_t* p = reinterpret_cast<uint32_t*>(row + (size_t)x0 * 3);
-            p[0] = w0;
-            p[1] = w1;
-            p[2] = w2;
+            pack12(v, reinterpret_cast<uint32_t*>(row + (size_t)x0 * 3));
         } else {
             for (int i = 0; i < 3 * n; ++i) row[(size_t)x0 * 3 + i] = (uint8_t)v[i];
         }

@@ -681,7 +681,11 @@ def multi_copy(plan):
 AUG_REC_WORDS, AUG_MAX_OPS = 20, 8
 AUG_OPS_WORDS = 4 + 2 * AUG_MAX_OPS
 AUG_MAX_KSIZE = 41
-AUG_OP_BLUR, AUG_OP_FDA = 7, 8
+# op types of a view's row (include/hiast_hip.h HIAST_AUG_OP_*, device_aug.OP_*)
+AUG_OP_LUT, AUG_OP_GRAY, AUG_OP_EQUALIZE, AUG_OP_CONTRAST, AUG_OP_SAT, AUG_OP_HUE, AUG_OP_BLUR, AUG_OP_FDA = range(1, 9)
+AUG_LEVEL1_OPS = (AUG_OP_LUT, AUG_OP_GRAY, AUG_OP_EQUALIZE)
+AUG_TABLE_OPS = (AUG_OP_EQUALIZE, AUG_OP_CONTRAST)        # a table built from the whole image: at most one per segment
+AUG_CLOSING_OPS = (AUG_OP_BLUR, AUG_OP_FDA)                # launches of their own after a segment's colour pass
 AUG_FDA_MAX_BORDER, AUG_FDA_BORDER_SHIFT, AUG_FDA_MIN_SIDE = 2, 40, 8
 
 
@@ -695,7 +699,7 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
     if recs.shape != (B, AUG_REC_WORDS) or ops.shape != (V, B, AUG_OPS_WORDS) or V < 1:
         raise ValueError("device_aug: record tables of shape %s / %s" % (recs.shape, ops.shape))
     for b in range(B):
-        r = [int(v) for v in recs[b]]
+        r = recs[b].tolist()
         kind = r[0]
         if kind == 1:
             inside(r[2], oh * ow, blob_n, "finished label", b)
@@ -733,23 +737,24 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
             if v.min() < 0 or v.max() >= n_in:
                 raise ValueError("device_aug: sample %d: %s table reads outside [0, %d)" % (b, nm, n_in))
         for k in range(V):
-            o = [int(v) for v in ops[k, b]]
+            o = ops[k, b].tolist()
             if o[0] != 0 or not 0 <= o[2] <= AUG_MAX_OPS:
                 raise ValueError("device_aug: sample %d view %d: kind %d with %d ops" % (b, k, o[0], o[2]))
             types = [o[4 + 2 * i] for i in range(o[2])]
-            if any(t not in (1, 2, 3, 4, 5, 6, 7, 8) for t in types) or (max(types, default=0) <= 3 and types.count(3) > 1):
+            if any(not AUG_OP_LUT <= t <= AUG_OP_FDA for t in types) or (
+                    all(t in AUG_LEVEL1_OPS for t in types) and types.count(AUG_OP_EQUALIZE) > 1):
                 raise ValueError("device_aug: sample %d view %d: op types %s" % (b, k, types))
             for i, t in enumerate(types):
                 par = o[5 + 2 * i]
-                if t == 1:
+                if t == AUG_OP_LUT:
                     inside(par, 256, blob_n, "view %d LUT %d" % (k, i), b)
-                elif t in (4, 5):          # contrast / saturation: the bits of a float64 factor
+                elif t in (AUG_OP_CONTRAST, AUG_OP_SAT):          # the bits of a float64 factor
                     if not np.isfinite(np.array([par], np.int64).view(np.float64)[0]):
                         raise ValueError("device_aug: sample %d view %d: op %d has a non-finite factor" % (b, k, i))
-                elif t == 6:
+                elif t == AUG_OP_HUE:
                     if not 0 <= par <= 255:
                         raise ValueError("device_aug: sample %d view %d: hue shift %d" % (b, k, par))
-                elif t == 7:               # blur: weights offset | ksize << 32
+                elif t == AUG_OP_BLUR:     # weights offset | ksize << 32
                     ksize, off = par >> 32, par & 0xFFFFFFFF
                     if not (3 <= ksize <= AUG_MAX_KSIZE and ksize % 2 == 1 and ksize // 2 < min(oh, ow)):
                         raise ValueError("device_aug: sample %d view %d: blur of %d taps on %dx%d" % (b, k, ksize, oh, ow))
@@ -757,7 +762,7 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
                     w = tabs[off:off + ksize].view(np.float32)
                     if not (np.isfinite(w).all() and np.array_equal(w, w[::-1])):
                         raise ValueError("device_aug: sample %d view %d: blur weights not finite and symmetric" % (b, k))
-                elif t == 8:               # FDA: blob offset of the target view | border << 40
+                elif t == AUG_OP_FDA:      # blob offset of the target view | border << 40
                     border, off = par >> AUG_FDA_BORDER_SHIFT, par & ((1 << AUG_FDA_BORDER_SHIFT) - 1)
                     if not (0 <= border <= AUG_FDA_MAX_BORDER and min(oh, ow) >= AUG_FDA_MIN_SIDE):
                         raise ValueError("device_aug: sample %d view %d: FDA of border %d on %dx%d" % (b, k, border, oh, ow))
@@ -781,78 +786,76 @@ def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch):
     return img, lbl
 
 
-def aug_colour_u8(img_u8, ops, blob, equalize=True):
-    """one view's op rows (ops int64 [B, 20] on the device, bounds-checked by the caller) on uint8 [B, H, W, 3] -> a new
-    tensor.  equalize: some row holds an Equalize (its histogram + table launches are skipped otherwise)"""
-    _req(img_u8, torch.uint8, 4, "img_u8")
-    _req(ops, torch.int64, 2, "ops")
-    _req(blob, torch.uint8, 1, "blob")
-    B, H, W, three = img_u8.shape
-    assert three == 3 and tuple(ops.shape) == (B, AUG_OPS_WORDS)
-    lib = _lib.load()
-    eq = torch.empty((B, 3, 256), dtype=torch.uint8, device=img_u8.device)
-    if equalize:
-        hist = torch.empty((B, 3, 256), dtype=torch.int32, device=img_u8.device)
-        check(lib.hiast_aug_hist_u8(_ptr(ops), _ptr(blob), _ptr(img_u8), _ptr(hist), _ptr(eq), B, H * W, _stream()),
-              "hiast_aug_hist_u8")
-    out = torch.empty_like(img_u8)
-    check(lib.hiast_aug_colour_u8(_ptr(ops), _ptr(blob), _ptr(eq), _ptr(img_u8), _ptr(out), B, H * W, _stream()),
-          "hiast_aug_colour_u8")
-    return out
-
-
 def _aug_segments(ops_view):
     """one view's op rows (numpy int64 [B, 20]) -> int32 [R, B, 4] = (from, to, stat, blur) per launch round and sample
-    (include/hiast_hip.h, K15b, K15c): a segment ends before a second table op (Equalize 3 / contrast 4) and after a
-    blur (7) or an FDA (8), whose index stands in the fourth word"""
-    B = ops_view.shape[0]
+    (include/hiast_hip.h, K15b, K15c): a segment ends before a second table op (Equalize / contrast) and after a blur
+    or an FDA, whose index stands in the fourth word.  A row of level-1 ops is one segment (0, n_ops, its Equalize | -1, -1)"""
+    rows = ops_view.tolist()              # (plain lists: this runs per view of every batch, numpy scalars cost more)
+    B = len(rows)
     rounds = []
     pos = [0] * B
-    n = [int(r[2]) if int(r[0]) == 0 else 0 for r in ops_view]
+    types = [r[4::2] for r in rows]
+    n = [r[2] if r[0] == 0 else 0 for r in rows]
     while True:
-        seg = np.full((B, 4), -1, np.int32)
         for b in range(B):
             i, stat = pos[b], -1
             while i < n[b]:
-                t = int(ops_view[b, 4 + 2 * i])
-                if t in (7, 8) or (t in (3, 4) and stat >= 0):
+                t = types[b][i]
+                if t in AUG_CLOSING_OPS or (t in AUG_TABLE_OPS and stat >= 0):
                     break
-                if t in (3, 4):
+                if t in AUG_TABLE_OPS:
                     stat = i
                 i += 1
-            blur = i if i < n[b] and int(ops_view[b, 4 + 2 * i]) in (7, 8) else -1
-            seg[b] = (pos[b], i, stat, blur)
+            blur = i if i < n[b] and types[b][i] in AUG_CLOSING_OPS else -1
+            rounds += (pos[b], i, stat, blur)
             pos[b] = i + (blur >= 0)
-        rounds.append(seg)
         if all(p >= m for p, m in zip(pos, n)):
-            return np.stack(rounds)
+            return np.array(rounds, np.int32).reshape(-1, B, 4)
 
 
-def aug2_view_u8(img_u8, ops, ops_h, blob, tabs):
-    """one view's op rows with level-2 ops (ops int64 [B, 20] on the device, ops_h the same rows on the host, bounds-checked
-    by the caller) on uint8 [B, H, W, 3] -> a new tensor: the first segment out of place, the others in place"""
+def _aug_batch_segments(ops_h):
+    """a batch's op rows (numpy int64 [V, B, 20]) -> (int32 [R, B, 4], [slice | None per view]): the launch rounds of the
+    views that need a colour launch one after the other (ONE upload per batch), and each view's rounds among them.  A
+    view needs none when no planned sample has ops and no finished view is to be copied in from the blob (view 0 of a
+    finished sample is copied by the geometry launch)"""
+    rounds, cuts, r0 = [np.zeros((0, ops_h.shape[1], 4), np.int32)], [], 0
+    for k, head in enumerate(ops_h[:, :, :3].tolist()):
+        if any(kind == 0 and n > 0 for kind, _, n in head) or (k > 0 and any(kind != 0 for kind, _, _ in head)):
+            rounds.append(_aug_segments(ops_h[k]))
+            cuts.append(slice(r0, r0 + len(rounds[-1])))
+            r0 = cuts[-1].stop
+        else:
+            cuts.append(None)
+    return np.concatenate(rounds), cuts
+
+
+def aug2_view_u8(img_u8, ops, ops_h, segs, segs_h, blob, tabs):
+    """one view's op rows (ops int64 [B, 20] on the device, ops_h the same rows on the host, segs int32 [R, B, 4] their
+    segments on the device, segs_h the same on the host; bounds-checked by the caller) on uint8 [B, H, W, 3] -> a new
+    tensor: the first segment out of place (finished views are copied in from the blob), the others in place"""
     _req(img_u8, torch.uint8, 4, "img_u8")
     _req(ops, torch.int64, 2, "ops")
+    _req(segs, torch.int32, 3, "segs")
     _req(blob, torch.uint8, 1, "blob")
     _req(tabs, torch.int32, 1, "tabs")
     B, H, W, three = img_u8.shape
     assert three == 3 and tuple(ops.shape) == tuple(ops_h.shape) == (B, AUG_OPS_WORDS)
+    assert tuple(segs.shape) == tuple(segs_h.shape) == (segs_h.shape[0], B, 4) and segs_h.shape[0] >= 1
     lib, dev = _lib.load(), img_u8.device
-    segs_h = _aug_segments(ops_h)
-    segs = torch.from_numpy(segs_h).pin_memory().to(dev, non_blocking=True)
     table = torch.empty((B, 3, 256), dtype=torch.uint8, device=dev)
-    hist = torch.empty((B, 3, 256), dtype=torch.int32, device=dev)
     out = torch.empty_like(img_u8)
-    tmp = None
-    for r in range(segs_h.shape[0]):
+    hist = tmp = None
+    for r, rows in enumerate(segs_h.tolist()):
         sg, src = segs[r], (img_u8 if r == 0 else out)
-        if (segs_h[r, :, 2] >= 0).any():
+        if any(stat >= 0 for _, _, stat, _ in rows):
+            if hist is None:
+                hist = torch.empty((B, 3, 256), dtype=torch.int32, device=dev)
             check(lib.hiast_aug2_table_u8(_ptr(ops), _ptr(sg), _ptr(blob), _ptr(src), _ptr(hist), _ptr(table), B, H * W,
                                           _stream()), "hiast_aug2_table_u8")
-        if r == 0 or (segs_h[r, :, 1] > segs_h[r, :, 0]).any():
+        if r == 0 or any(to > frm for frm, to, _, _ in rows):
             check(lib.hiast_aug2_colour_u8(_ptr(ops), _ptr(sg), _ptr(blob), _ptr(table), _ptr(src), _ptr(out), B, H * W,
                                            _stream()), "hiast_aug2_colour_u8")
-        closing = [int(ops_h[b, 4 + 2 * i]) for b, i in enumerate(segs_h[r, :, 3]) if i >= 0]
+        closing = [int(ops_h[b, 4 + 2 * i]) for b, (_, _, _, i) in enumerate(rows) if i >= 0]
         if AUG_OP_BLUR in closing:
             if tmp is None:
                 tmp = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
@@ -901,7 +904,9 @@ def aug3_fda_u8(img_u8, ops, seg, blob):
 
 def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
     """HOST tensors of a collated device_aug batch (device_aug.build_batch_tables) -> ([uint8 [B, oh, ow, 3] per view],
-    uint8 label [B, oh, ow]) on `device`: four uploads, then geometry + one colour pass per view"""
+    uint8 label [B, oh, ow]) on `device`: four uploads + one of the views' segments where a view has a colour launch, then
+    geometry + per view the launch rounds of its segments (rows of level-1 ops: one round, the table launches only if a
+    row equalises, one colour pass)"""
     for t, dt, nm in ((blob, torch.uint8, "blob"), (tabs, torch.int32, "tabs"), (recs, torch.int64, "recs"),
                       (ops, torch.int64, "ops")):
         if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != dt or not t.is_contiguous():
@@ -912,19 +917,13 @@ def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
     _aug_check_tables(blob.numel(), tabs.numpy(), recs_h, ops_h, oh, ow, max_ch)
     up = lambda t: (t if t.is_pinned() else t.pin_memory()).to(device, non_blocking=True)      # noqa: E731
     blob_d, tabs_d, recs_d, ops_d = up(blob), up(tabs), up(recs), up(ops)
+    segs_h, cuts = _aug_batch_segments(ops_h)              # (cut while the blob travels)
+    segs_d = h2d_async(segs_h, device) if len(segs_h) else None
     cur, lbl = aug_geometry_u8(blob_d, tabs_d, recs_d, oh, ow, max_ch)
     views = []
-    for k in range(ops_h.shape[0]):
-        planned = ops_h[k, :, 0] == 0
-        has_ops = bool((ops_h[k, planned, 2] > 0).any())
-        if has_ops or (k > 0 and not planned.all()):       # (finished samples: view k is copied in from the blob)
-            n = ops_h[k, :, 2]
-            live = (np.arange(AUG_MAX_OPS)[None, :] < n[:, None]) & planned[:, None]
-            if bool(((ops_h[k][:, 4::2] > 3) & live).any()):      # level 2: ColorJitter / GaussianBlur ops, in segments
-                cur = aug2_view_u8(cur, ops_d[k], ops_h[k], blob_d, tabs_d)
-            else:
-                eq = bool(((ops_h[k][:, 4::2] == 3) & live).any())
-                cur = aug_colour_u8(cur, ops_d[k], blob_d, equalize=eq)
+    for k, cut in enumerate(cuts):
+        if cut is not None:
+            cur = aug2_view_u8(cur, ops_d[k], ops_h[k], segs_d[cut], segs_h[cut], blob_d, tabs_d)
         views.append(cur)
     return views, lbl
 

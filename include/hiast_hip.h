@@ -536,13 +536,12 @@ int hiast_normalize_u8(const uint8_t* img, float* out, int B, int64_t HW, const 
  *        offsets hlo, hn, hk, h_taps, vlo, vn, vk, v_taps (first tap / tap count / [out][taps] 22-bit fixed-point
  *        weights per output column / row: Pillow's 8-bit resample), nx, ny (nearest source index per output column / row)
  *   ops  [B][HIAST_AUG_OPS_WORDS] of ONE view: kind, blob offset of the finished view (kind 1), n_ops, 0, then
- *        (type, blob offset of a 256-entry table) x HIAST_AUG_MAX_OPS; at most one HIAST_AUG_OP_EQUALIZE per row.
+ *        (type, blob offset of a 256-entry table) x HIAST_AUG_MAX_OPS; at most one HIAST_AUG_OP_EQUALIZE per row of
+ *        level-1 ops.  The rows of every level are executed by the K15b entries: a row of level-1 ops is the one segment
+ *        (0, n_ops, index of its Equalize | -1, -1).
  * hiast_aug_geometry_u8: CopyPaste select on load (table[paste_lbl] ? paste : own), flipped read, horizontal pass into
  *   tmp [B][max_ch][ow][3] (rounded to uint8), vertical pass -> img_out uint8 [B][oh][ow][3]; label gather through the
- *   same select -> lbl_out uint8 [B][oh][ow].  Two launches.
- * hiast_aug_hist_u8: per sample with an Equalize in its row, the per-channel histogram of `in` after the ops before it
- *   (hist uint32 [B][3][256], zeroed here) and cv2.equalizeHist's tables from it (eq_lut uint8 [B][3][256]).
- * hiast_aug_colour_u8: a view's op row on in uint8 [B][HW][3] -> out (a different buffer). */
+ *   same select -> lbl_out uint8 [B][oh][ow].  Two launches. */
 #define HIAST_AUG_REC_WORDS 20
 #define HIAST_AUG_MAX_OPS 8
 #define HIAST_AUG_OPS_WORDS (4 + 2 * HIAST_AUG_MAX_OPS)
@@ -551,14 +550,11 @@ int hiast_normalize_u8(const uint8_t* img, float* out, int B, int64_t HW, const 
 #define HIAST_AUG_OP_EQUALIZE 3
 int hiast_aug_geometry_u8(const int64_t* recs, const uint8_t* blob, const int32_t* tabs, uint8_t* tmp,
                           uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow, hiast_stream_t stream);
-int hiast_aug_hist_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* in, uint32_t* hist, uint8_t* eq_lut,
-                      int B, int64_t HW, hiast_stream_t stream);
-int hiast_aug_colour_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* eq_lut, const uint8_t* in,
-                        uint8_t* out, int B, int64_t HW, hiast_stream_t stream);
 
-/* ---- K15b: level 2 of the device-side sample path (cfg.dataset.device_aug_level: 2) ------------------------------
- * ColorJitter and GaussianBlur as plan ops, byte-identical to hiast_amd/sseg/datasets/augmentations.py.  Further op
- * types of an ops row; the second word of the pair is
+/* ---- K15b: the colour ops of the device-side sample path, every level -------------------------------------------
+ * Level 1: LUT, OpenCV's fixed-point gray, cv2.equalizeHist (per-channel histogram -> float64 table, rint).  Level 2
+ * (cfg.dataset.device_aug_level: 2): ColorJitter and GaussianBlur as plan ops.  All byte-identical to
+ * hiast_amd/sseg/datasets/augmentations.py.  The level-2 op types of an ops row; the second word of the pair is
  *   HIAST_AUG_OP_CONTRAST  the bits of the float64 factor (the table is built on the device from the gray mean of the
  *                          image at that point of the chain)
  *   HIAST_AUG_OP_SAT       the bits of the float64 factor
@@ -567,7 +563,9 @@ int hiast_aug_colour_u8(const int64_t* ops, const uint8_t* blob, const uint8_t* 
  *                          3..HIAST_AUG_MAX_KSIZE, ksize / 2 < min(H, W)
  * The host cuts a row into segments, one launch round each: seg int32 [B][4] = (from, to, stat, blur): ops [from, to)
  * are pointwise except for at most one table op (Equalize / contrast) at index stat (-1: none); a blur at index
- * blur (-1: none) follows them.  A sample whose segment is empty is skipped.  Any number of table ops per row.
+ * blur (-1: none) follows them.  A sample whose segment is empty is skipped.  Any number of table ops per row
+ * that holds a level-2 op.  A batch of level-1 rows is one round: hiast_aug2_table_u8 only if some row has an Equalize,
+ * then one hiast_aug2_colour_u8 (in != out).
  * hiast_aug2_table_u8: per sample with a table op, the histogram of `in` after ops [from, stat) (hist uint32
  *   [B][3][256], zeroed here; contrast: the gray histogram in bins 0..255) and the op's table (uint8 [B][3][256]).
  * hiast_aug2_colour_u8: ops [from, to) on in uint8 [B][HW][3] -> out.  in != out: every sample is written (finished

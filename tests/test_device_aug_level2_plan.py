@@ -257,3 +257,37 @@ def test_segments_cut_at_table_ops_and_blurs():
     assert segs[:, 1].tolist() == [[0, 0, -1, 0], [1, 1, -1, -1], [1, 1, -1, -1]]
     assert segs[:, 2].tolist() == [[0, 0, -1, -1]] * 3
     assert segs[:, 3].tolist() == [[0, 1, 0, -1], [1, 2, 1, 2], [3, 3, -1, 3]]
+
+
+def _op_rows(lists, finished=()):
+    rows = np.zeros((len(lists), DA.OPS_WORDS), np.int64)
+    for b, types in enumerate(lists):
+        rows[b, 2] = len(types)
+        rows[b, 4:4 + 2 * len(types):2] = types
+    rows[list(finished), 0] = DA.KIND_FINISHED
+    return rows
+
+
+def test_level1_rows_are_one_segment_and_a_batch_uploads_its_views_segments_once():
+    """rows of level-1 ops run through the segment kernels as ONE round (0, n, index of the Equalize | -1, -1); the
+    segment tensor aug_batch_u8 uploads once per batch is the views' own segments one after the other"""
+    from hiast_amd import kernels as K
+    E, S, B, L, G = DA.OP_EQUALIZE, DA.OP_SAT, DA.OP_BLUR, DA.OP_LUT, DA.OP_GRAY
+    rows = _op_rows([[L], [G], [E], [L, E, G], [], [L, E]], finished=[5])      # (a finished row's ops are not read)
+    segs = K._aug_segments(rows)
+    assert segs.dtype == np.int32 and segs.shape == (1, 6, 4)
+    assert segs[0].tolist() == [[0, 1, -1, -1], [0, 1, -1, -1], [0, 1, 0, -1], [0, 3, 1, -1], [0, 0, -1, -1], [0, 0, -1, -1]]
+    ops = np.stack([_op_rows([[L, E, G], [L]]), _op_rows([[S, B, E], []])])
+    both, cuts = K._aug_batch_segments(ops)
+    assert both.dtype == np.int32 and both.shape == (3, 2, 4) and cuts == [slice(0, 1), slice(1, 3)]
+    for k in range(2):
+        assert np.array_equal(both[cuts[k]], K._aug_segments(ops[k])), k
+    assert both[cuts[0]][:, 0].tolist() == [[0, 3, 1, -1]]
+    assert both[cuts[1]][:, 0].tolist() == [[0, 1, -1, 1], [2, 3, 2, -1]]
+    # no ops and nothing finished: no colour launch and nothing to upload; a finished sample: view 1 is copied in from
+    # the blob by view 1's colour launch (view 0 by the geometry)
+    none, cuts = K._aug_batch_segments(np.stack([_op_rows([[], []]), _op_rows([[], []])]))
+    assert none.shape == (0, 2, 4) and cuts == [None, None]
+    done = np.stack([_op_rows([[], []], finished=[1])] * 2)
+    one, cuts = K._aug_batch_segments(done)
+    assert cuts == [None, slice(0, 1)] and one.tolist() == [[[0, 0, -1, -1]] * 2]

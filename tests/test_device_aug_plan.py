@@ -200,3 +200,24 @@ def test_copy_paste_select_then_crop_equals_run_original_then_crop(golden):
     assert pasted > 0
     s2 = np.random.get_state()
     assert state[0] == s2[0] and np.array_equal(state[1], s2[1]) and state[2:] == s2[2:]
+
+
+def test_op_constants_are_the_same_in_the_planner_the_wrappers_and_the_header():
+    """the op types and limits of a view's op row are written three times (device_aug.py for the planner, kernels.py for
+    the host checks and the launch rounds, include/hiast_hip.h for the kernels): they must be one set of numbers"""
+    import os
+    import re
+    from hiast_amd import kernels as K
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    txt = open(os.path.join(root, "include", "hiast_hip.h")).read()
+    hdr = {m.group(1): eval(m.group(2).replace("HIAST_AUG_MAX_OPS", "8"), {})
+           for m in re.finditer(r"^#define HIAST_AUG_(\w+) (.+)$", txt, flags=re.M)}
+    names = ("OP_LUT", "OP_GRAY", "OP_EQUALIZE", "OP_CONTRAST", "OP_SAT", "OP_HUE", "OP_BLUR", "OP_FDA", "MAX_OPS", "MAX_KSIZE",
+             "OPS_WORDS", "REC_WORDS", "FDA_MAX_BORDER", "FDA_BORDER_SHIFT")
+    assert sorted(hdr) == sorted(names)
+    for n in names:
+        assert getattr(K, "AUG_" + n) == getattr(DA, n) == hdr[n], n
+    assert K.AUG_FDA_MIN_SIDE == DA.FDA_MIN_SIDE
+    assert sorted(hdr[n] for n in names if n.startswith("OP_")) == list(range(1, 9))
+    assert K.AUG_LEVEL1_OPS == (DA.OP_LUT, DA.OP_GRAY, DA.OP_EQUALIZE)
+    assert K.AUG_TABLE_OPS == (DA.OP_EQUALIZE, DA.OP_CONTRAST) and K.AUG_CLOSING_OPS == (DA.OP_BLUR, DA.OP_FDA)

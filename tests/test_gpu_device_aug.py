@@ -1,4 +1,4 @@
-"""cfg.dataset.device_aug on the device (hiast_amd/csrc/sample_aug.hip): the kernels against the numpy executor of the same
+"""cfg.dataset.device_aug on the device (hiast_amd/csrc/sample_aug.hip, the colour ops in sample_aug2.hip): the kernels against the numpy executor of the same
 plan (device_aug.execute_plan_host, itself pinned to augmentations.aug() and Pillow in tests/test_device_aug_plan.py), and
 the whole path — dataset, collate, assemble_device_batch, one training iteration — against the worker path.  Equality
 everywhere: bytes for uint8, bits for float32."""
@@ -147,6 +147,29 @@ def test_colour_ops_alone_and_composed(K, shape):
     _compare(K, two)
     want = DA.execute_plan_host(cases[4][0], spike, lbl)[0][0]
     assert set(np.unique(want[..., 2])) == {0, 255}                 # (the spike case is the one it claims to be)
+
+
+def test_level1_batches_issue_the_level1_launches(K, monkeypatch):
+    """rows of level-1 ops go through the segment kernels in ONE round: geometry, the table launches only when a row
+    equalises, one colour pass; a batch without ops and without finished samples is the geometry alone"""
+    img, lbl = _frame(23, 48, 96)
+    lut = A._brightness_contrast_lut(1.3, 0.0)
+
+    def plan(*ops):
+        p = DA.plan_sample(A.resize(32, 64), (48, 96))
+        p[0]["ops"] += list(ops)
+        return p
+    L, E = ("lut", lut), ("equalize",)
+    geometry, table, colour = "hiast_aug_geometry_u8", "hiast_aug2_table_u8", "hiast_aug2_colour_u8"
+    seen = []
+    check = K.check
+    monkeypatch.setattr(K, "check", lambda rc, what: (seen.append(what), check(rc, what))[1])
+    for rows, want in (([[L], [L]], [geometry, colour]),
+                       ([[L], [L, E]], [geometry, table, colour]),
+                       ([[], []], [geometry])):
+        del seen[:]
+        _compare(K, [(plan(*ops), img, lbl, None) for ops in rows])
+        assert seen == want, (rows, seen)
 
 
 def test_bad_tables_are_refused_on_the_host(K):
