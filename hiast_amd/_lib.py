@@ -100,7 +100,9 @@ SIGNATURES = {
     "hiast_maxpool3x3s2_nhwc_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "hiast_multi_copy": (c_int, [c_vp, c_int, c_vp]),
     "hiast_aug_geometry_u8": (c_int, [c_vp] * 6 + [c_int] * 4 + [c_vp]),
-    "hiast_aug2_table_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
+    "hiast_aug_geometry_store_u8": (c_int, [c_vp] * 7 + [c_int] * 4 + [c_vp]),
+    "hiast_normalize_gather_u8": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp]),
+    "hiast_aug2_table_u8":(c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
     "hiast_aug2_colour_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
     "hiast_aug2_blur_u8": (c_int, [c_vp] * 5 + [c_int] * 3 + [c_vp]),
     "hiast_aug3_fda_workspace_bytes": (c_sz, [c_int] * 3),

@@ -255,6 +255,20 @@ __device__ __forceinline__ int band_start(float scale, int j, int in, int out)
     return Y;
 }
 
+// K14's arithmetic on one image (uint8 [HW][3] -> float32 [3][HW]), grid-stride along blockIdx.x: torch's operations in
+// torch's order, v = float(u8) / 255; out = (v - mean) / std.  One body for hiast_normalize_u8 (misc.hip) and
+// hiast_normalize_gather_u8 (sample_aug.hip), whose outputs must agree bit for bit.
+__device__ __forceinline__ void normalize_image_u8(const unsigned char* __restrict__ src, float* __restrict__ dst, long long HW,
+                                                   float m0, float m1, float m2, float s0, float s1, float s2)
+{
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
+        const float r = (float)src[p * 3] / 255.0f, g = (float)src[p * 3 + 1] / 255.0f, bl = (float)src[p * 3 + 2] / 255.0f;
+        dst[p] = (r - m0) / s0;
+        dst[HW + p] = (g - m1) / s1;
+        dst[2 * HW + p] = (bl - m2) / s2;
+    }
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // 64-bit wave reductions (all 64 lanes participate)

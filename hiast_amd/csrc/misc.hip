@@ -49,14 +49,7 @@ __global__ __launch_bounds__(256) void normalize_u8_kernel(const unsigned char* 
                                                            float s2)
 {
     const int b = blockIdx.y;
-    const unsigned char* src = img + (size_t)b * HW * 3;
-    float* dst = out + (size_t)b * 3 * HW;
-    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
-        const float r = (float)src[p * 3] / 255.0f, g = (float)src[p * 3 + 1] / 255.0f, bl = (float)src[p * 3 + 2] / 255.0f;
-        dst[p] = (r - m0) / s0;
-        dst[HW + p] = (g - m1) / s1;
-        dst[2 * HW + p] = (bl - m2) / s2;
-    }
+    normalize_image_u8(img + (size_t)b * HW * 3, out + (size_t)b * 3 * HW, HW, m0, m1, m2, s0, s1, s2);
 }
 
 // copy a list of small tensors (the BatchNorm buffers the EMA teacher takes over from the student,

@@ -9,31 +9,56 @@
 // blob (hiast_hip.h), as hiast_ema_update / hiast_multi_copy do with pointers.
 // Table indices are clamped to the sample's extent before they address memory: the host wrapper rejects a table that
 // points outside, the clamp keeps a wrong table from leaving the buffers.
+// Device-resident frames (hiast_amd/sseg/datasets/device_store.py): a record of kind 2 addresses its window, and its
+// CopyPaste source window, in place in the STORE of decoded frames instead of the blob: the same reads with the frame's
+// width as the row stride (record word 19) instead of cw.  The kernels take the store as an argument (null for
+// hiast_aug_geometry_u8, which then knows kinds 0 and 1 only); the paste table and all tap tables stay in blob / tabs.
 #include "aug_common.h"
 
 namespace hiast {
 
 enum { R_KIND, R_IMG, R_LBL, R_PIMG, R_PLBL, R_PTAB, R_CH, R_CW, R_FLIP, R_HLO, R_HN, R_HK, R_HT, R_VLO, R_VN, R_VK, R_VT,
-       R_NX, R_NY };
+       R_NX, R_NY, R_STRIDE };
+enum { KIND_PLAN = 0, KIND_FINISHED = 1, KIND_STORE = HIAST_STORE_KIND };
+static_assert(R_STRIDE == HIAST_STORE_REC_STRIDE && R_STRIDE < HIAST_AUG_REC_WORDS, "the stride is the record's spare word");
 constexpr int REC = HIAST_AUG_REC_WORDS;
 constexpr int PBITS = 22;
 
 __device__ __forceinline__ unsigned clip8(int v) { return (unsigned)clampi(v >> PBITS, 0, 255); }
 
+// where a planned sample's window lies: the bytes handed over in the blob (row stride cw) or, for a KIND_STORE record
+// of a launch with a store, a window of a resident frame (row stride = the frame's width, never below cw)
+struct Window {
+    const uint8_t* base;
+    size_t stride;
+    bool planned;
+};
+__device__ __forceinline__ Window window_of(const int64_t* r, const uint8_t* blob, const uint8_t* store)
+{
+    Window w;
+    const bool st = store != nullptr && r[R_KIND] == KIND_STORE;
+    const int64_t cw = r[R_CW];
+    w.planned = st || r[R_KIND] == KIND_PLAN;
+    w.base = st ? store : blob;
+    w.stride = (size_t)(st && r[R_STRIDE] > cw ? r[R_STRIDE] : cw);
+    return w;
+}
+
 // horizontal pass: one thread per (output column, source row) of a planned sample -> tmp [B][max_ch][ow][3]
 __global__ __launch_bounds__(256) void aug_hpass_kernel(const int64_t* __restrict__ recs, const uint8_t* __restrict__ blob,
-                                                        const int32_t* __restrict__ tabs, uint8_t* __restrict__ tmp,
-                                                        int max_ch, int ow)
+                                                        const uint8_t* __restrict__ store, const int32_t* __restrict__ tabs,
+                                                        uint8_t* __restrict__ tmp, int max_ch, int ow)
 {
     const int64_t* r = recs + (size_t)blockIdx.z * REC;
-    if (r[R_KIND] != 0) return;
+    const Window win = window_of(r, blob, store);
+    if (!win.planned) return;
     const int ch = (int)r[R_CH], cw = (int)r[R_CW], row = blockIdx.y;
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (row >= ch || x >= ow) return;
     const bool flip = r[R_FLIP] != 0, paste = r[R_PIMG] >= 0;
-    const uint8_t* img = blob + r[R_IMG] + (size_t)row * cw * 3;
-    const uint8_t* pimg = paste ? blob + r[R_PIMG] + (size_t)row * cw * 3 : img;
-    const uint8_t* plbl = paste ? blob + r[R_PLBL] + (size_t)row * cw : img;
+    const uint8_t* img = win.base + r[R_IMG] + (size_t)row * win.stride * 3;
+    const uint8_t* pimg = paste ? win.base + r[R_PIMG] + (size_t)row * win.stride * 3 : img;
+    const uint8_t* plbl = paste ? win.base + r[R_PLBL] + (size_t)row * win.stride : img;
     const uint8_t* ptab = paste ? blob + r[R_PTAB] : img;
     const int T = (int)r[R_HT], lo = tabs[r[R_HLO] + x], n = tabs[r[R_HN] + x];
     const int32_t* k = tabs + r[R_HK] + (size_t)x * T;
@@ -57,7 +82,8 @@ __global__ __launch_bounds__(256) void aug_hpass_kernel(const int64_t* __restric
 // thread when ow*3 is a multiple of 4) + the label gather + the copy of finished (host-augmented) samples
 template <int VEC>
 __global__ __launch_bounds__(256) void aug_vpass_kernel(const int64_t* __restrict__ recs, const uint8_t* __restrict__ blob,
-                                                        const int32_t* __restrict__ tabs, const uint8_t* __restrict__ tmp,
+                                                        const uint8_t* __restrict__ store, const int32_t* __restrict__ tabs,
+                                                        const uint8_t* __restrict__ tmp,
                                                         uint8_t* __restrict__ img_out, uint8_t* __restrict__ lbl_out,
                                                         int max_ch, int oh, int ow)
 {
@@ -68,7 +94,8 @@ __global__ __launch_bounds__(256) void aug_vpass_kernel(const int64_t* __restric
     uint8_t* dimg = img_out + ((size_t)b * oh + y) * rowb;
     uint8_t* dlbl = lbl_out + ((size_t)b * oh + y) * ow;
     const int stride = gridDim.x * 256;
-    if (r[R_KIND] != 0) {                   // finished view 0 + label of a host-augmented sample
+    const Window win = window_of(r, blob, store);
+    if (!win.planned) {                     // finished view 0 + label of a host-augmented sample
         const uint8_t* s = blob + r[R_IMG] + (size_t)y * rowb;
         if (q < rowb) {
             if (VEC == 4) *reinterpret_cast<uint32_t*>(dimg + q) = *reinterpret_cast<const uint32_t*>(s + q);
@@ -108,8 +135,8 @@ __global__ __launch_bounds__(256) void aug_vpass_kernel(const int64_t* __restric
     }
     const bool flip = r[R_FLIP] != 0, paste = r[R_PIMG] >= 0;
     const int sy = clampi(tabs[r[R_NY] + y], 0, ch - 1);
-    const uint8_t* lbl = blob + r[R_LBL] + (size_t)sy * cw;
-    const uint8_t* plbl = paste ? blob + r[R_PLBL] + (size_t)sy * cw : lbl;
+    const uint8_t* lbl = win.base + r[R_LBL] + (size_t)sy * win.stride;
+    const uint8_t* plbl = paste ? win.base + r[R_PLBL] + (size_t)sy * win.stride : lbl;
     const uint8_t* ptab = paste ? blob + r[R_PTAB] : lbl;
     for (int x = blockIdx.x * 256 + threadIdx.x; x < ow; x += stride) {
         const int sx = clampi(tabs[r[R_NX] + x], 0, cw - 1);
@@ -123,25 +150,65 @@ __global__ __launch_bounds__(256) void aug_vpass_kernel(const int64_t* __restric
     }
 }
 
+// B frames of HW pixels at offsets[b] of the store -> out float32 [B][3][HW]: K14's arithmetic (common.h)
+__global__ __launch_bounds__(256) void normalize_gather_u8_kernel(const uint8_t* __restrict__ store,
+                                                                  const int64_t* __restrict__ offsets, float* __restrict__ out,
+                                                                  long long HW, float m0, float m1, float m2, float s0, float s1,
+                                                                  float s2)
+{
+    const int b = blockIdx.y;
+    const int64_t off = offsets[b];
+    normalize_image_u8(store + (off < 0 ? 0 : off), out + (size_t)b * 3 * HW, HW, m0, m1, m2, s0, s1, s2);
+}
+
 }  // namespace hiast
+
+// the two launches of the geometry pass; store == nullptr: kinds 0 and 1 only (hiast_aug_geometry_u8)
+static int aug_geometry_launch(const int64_t* recs, const uint8_t* blob, const uint8_t* store, const int32_t* tabs, uint8_t* tmp,
+                               uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow, hiast_stream_t stream)
+{
+    if (B <= 0 || max_ch <= 0 || oh <= 0 || ow <= 0) return HIAST_E_ARG;
+    if (B > 65535 || max_ch > 65535 || oh > 65535 || ow > (1 << 20)) return HIAST_E_RANGE;
+    hipLaunchKernelGGL(hiast::aug_hpass_kernel, dim3((ow + 255) / 256, max_ch, B), dim3(256), 0, (hipStream_t)stream, recs,
+                       blob, store, tabs, tmp, max_ch, ow);
+    HIAST_CHECK_LAUNCH();
+    const int rowb = ow * 3;
+    if (rowb % 4 == 0 && ((((uintptr_t)tmp) | ((uintptr_t)img_out) | ((uintptr_t)blob)) & 3) == 0)
+        hipLaunchKernelGGL(hiast::aug_vpass_kernel<4>, dim3((rowb / 4 + 255) / 256, oh, B), dim3(256), 0, (hipStream_t)stream,
+                           recs, blob, store, tabs, tmp, img_out, lbl_out, max_ch, oh, ow);
+    else
+        hipLaunchKernelGGL(hiast::aug_vpass_kernel<1>, dim3((rowb + 255) / 256, oh, B), dim3(256), 0, (hipStream_t)stream,
+                           recs, blob, store, tabs, tmp, img_out, lbl_out, max_ch, oh, ow);
+    HIAST_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int hiast_aug_geometry_u8(const int64_t* recs, const uint8_t* blob, const int32_t* tabs, uint8_t* tmp,
                                      uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow,
                                      hiast_stream_t stream)
 {
     if (!recs || !blob || !tabs || !tmp || !img_out || !lbl_out) return HIAST_E_ARG;
-    if (B <= 0 || max_ch <= 0 || oh <= 0 || ow <= 0) return HIAST_E_ARG;
-    if (B > 65535 || max_ch > 65535 || oh > 65535 || ow > (1 << 20)) return HIAST_E_RANGE;
-    hipLaunchKernelGGL(hiast::aug_hpass_kernel, dim3((ow + 255) / 256, max_ch, B), dim3(256), 0, (hipStream_t)stream, recs,
-                       blob, tabs, tmp, max_ch, ow);
-    HIAST_CHECK_LAUNCH();
-    const int rowb = ow * 3;
-    if (rowb % 4 == 0 && ((((uintptr_t)tmp) | ((uintptr_t)img_out) | ((uintptr_t)blob)) & 3) == 0)
-        hipLaunchKernelGGL(hiast::aug_vpass_kernel<4>, dim3((rowb / 4 + 255) / 256, oh, B), dim3(256), 0, (hipStream_t)stream,
-                           recs, blob, tabs, tmp, img_out, lbl_out, max_ch, oh, ow);
-    else
-        hipLaunchKernelGGL(hiast::aug_vpass_kernel<1>, dim3((rowb + 255) / 256, oh, B), dim3(256), 0, (hipStream_t)stream,
-                           recs, blob, tabs, tmp, img_out, lbl_out, max_ch, oh, ow);
+    return aug_geometry_launch(recs, blob, nullptr, tabs, tmp, img_out, lbl_out, B, max_ch, oh, ow, stream);
+}
+
+extern "C" int hiast_aug_geometry_store_u8(const int64_t* recs, const uint8_t* blob, const uint8_t* store, const int32_t* tabs,
+                                           uint8_t* tmp, uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow,
+                                           hiast_stream_t stream)
+{
+    if (!recs || !blob || !store || !tabs || !tmp || !img_out || !lbl_out) return HIAST_E_ARG;
+    return aug_geometry_launch(recs, blob, store, tabs, tmp, img_out, lbl_out, B, max_ch, oh, ow, stream);
+}
+
+extern "C" int hiast_normalize_gather_u8(const uint8_t* store, const int64_t* offsets, float* out, int B, int64_t HW,
+                                         const float* mean, const float* std, hiast_stream_t stream)
+{
+    if (!store || !offsets || !out || !mean || !std) return HIAST_E_ARG;
+    if (B <= 0 || HW <= 0) return HIAST_E_ARG;
+    if (B > 65535) return HIAST_E_RANGE;
+    long long nb = (HW + 256 * 4 - 1) / (256 * 4);
+    nb = nb < 1 ? 1 : (nb > 1024 ? 1024 : nb);
+    hipLaunchKernelGGL(hiast::normalize_gather_u8_kernel, dim3((unsigned)nb, B), dim3(256), 0, (hipStream_t)stream, store,
+                       offsets, out, (long long)HW, mean[0], mean[1], mean[2], std[0], std[1], std[2]);
     HIAST_CHECK_LAUNCH();
     return 0;
 }

@@ -649,6 +649,36 @@ def normalize_u8(img_u8, mean, std):
     return out
 
 
+def normalize_gather_u8(store, offsets, H, W, mean, std):
+    """normalize_u8 of B frames of H x W that lie at `offsets` (int64 [B], element offsets of their first bytes) in the uint8
+    buffer `store` of device-resident frames -> float32 [B, 3, H, W], one launch, bit-identical to normalize_u8 of the
+    stacked frames.  offsets: a HOST tensor (checked here, uploaded through pinned memory) or a device tensor (checked
+    with one read-back)"""
+    _req(store, torch.uint8, 1, "store")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1:
+        raise TypeError("normalize_gather_u8: offsets must be an int64 vector")
+    B, H, W = offsets.numel(), int(H), int(W)
+    assert len(mean) == 3 and len(std) == 3
+    if H <= 0 or W <= 0:
+        raise ValueError("normalize_gather_u8: frames of %dx%d" % (H, W))
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=store.device)
+    if B == 0:
+        return out
+    lo, hi = int(offsets.min()), int(offsets.max())
+    if lo < 0 or hi + H * W * 3 > store.numel():
+        raise ValueError("normalize_gather_u8: frames of %dx%d at offsets %d..%d outside the store of %d bytes"
+                         % (H, W, lo, hi, store.numel()))
+    if not offsets.is_cuda:
+        offsets = h2d_async(offsets.numpy(), store.device)
+    elif offsets.device != store.device or not offsets.is_contiguous():
+        raise ValueError("normalize_gather_u8: offsets must be contiguous and on the store's device")
+    m = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s_ = (ctypes.c_float * 3)(*[float(v) for v in std])
+    check(_lib.load().hiast_normalize_gather_u8(_ptr(store), _ptr(offsets), _ptr(out), B, H * W, m, s_, _stream()),
+          "hiast_normalize_gather_u8")
+    return out
+
+
 class CopyPlan:
     """device table for copying a fixed list of (small) tensors in one launch"""
 
@@ -689,9 +719,42 @@ AUG_CLOSING_OPS = (AUG_OP_BLUR, AUG_OP_FDA)                # launches of their o
 AUG_FDA_MAX_BORDER, AUG_FDA_BORDER_SHIFT, AUG_FDA_MIN_SIDE = 2, 40, 8
 
 
-def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
+AUG_KIND_STORE, AUG_REC_STRIDE = 2, 19                   # include/hiast_hip.h HIAST_STORE_KIND, HIAST_STORE_REC_STRIDE
+
+
+def _aug_check_store_windows(r, b, store):
+    """a KIND_STORE record (list of its words) against the store = (its size in bytes, the residency table int64 [n, 4] =
+    (image offset, label offset, H, W), -1 = not resident): every window inside ONE resident frame and inside the store"""
+    if store is None:
+        raise ValueError("device_aug: sample %d: a record over device-resident frames, but no store is given" % b)
+    store_n, frames = store
+    ch, cw, stride = r[6], r[7], r[AUG_REC_STRIDE]
+    if stride < cw:
+        raise ValueError("device_aug: sample %d: row stride %d below the window's width %d" % (b, stride, cw))
+    wins = [(r[1], 3, 0, "image"), (r[2], 1, 1, "label")]
+    if r[3] >= 0 or r[4] >= 0 or r[5] >= 0:
+        wins += [(r[3], 3, 0, "paste image"), (r[4], 1, 1, "paste label")]
+    for off, px, col, what in wins:
+        if off < 0:
+            raise ValueError("device_aug: sample %d: %s window at the negative offset %d" % (b, what, off))
+        if off + ((ch - 1) * stride + cw) * px > store_n:
+            raise ValueError("device_aug: sample %d: %s window [%d, %dx%d, stride %d) runs past the store's end %d"
+                             % (b, what, off, ch, cw, stride, store_n))
+        starts = np.sort(frames[frames[:, col] >= 0, col])
+        j = int(np.searchsorted(starts, off, "right")) - 1
+        if j < 0:
+            raise ValueError("device_aug: sample %d: %s window at %d lies in no resident frame" % (b, what, off))
+        fo, fh, fw = (int(v) for v in frames[frames[:, col] == starts[j]][0][[col, 2, 3]])
+        y1, x1 = divmod((off - fo) // px, fw)
+        if (off - fo) % px or stride != fw or x1 + cw > fw or y1 + ch > fh:
+            raise ValueError("device_aug: sample %d: %s window (%d, %d) + %dx%d, stride %d, runs past its frame of %dx%d"
+                             % (b, what, y1, x1, ch, cw, stride, fh, fw))
+
+
+def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch, store=None):
     """host-side bounds of a batch's record tables (numpy views of the HOST tensors): every offset + extent inside its
-    blob, every table index inside the sample's window — a kernel that reads outside can take the node down"""
+    blob, every table index inside the sample's window — a kernel that reads outside can take the node down.  store:
+    (bytes, residency table) of the device-resident frames that records of kind 2 address (_aug_check_store_windows)"""
     def inside(off, n, size, what, b):
         if off < 0 or off % 4 != 0 or off + n > size:
             raise ValueError("device_aug: sample %d: %s [%d, +%d) outside its blob of %d" % (b, what, off, n, size))
@@ -708,17 +771,22 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
                     raise ValueError("device_aug: sample %d: view %d of a finished sample has kind %d" % (b, k, int(ops[k, b, 0])))
                 inside(int(ops[k, b, 1]), oh * ow * 3, blob_n, "finished view %d" % k, b)
             continue
-        if kind != 0:
+        if kind not in (0, AUG_KIND_STORE):
             raise ValueError("device_aug: sample %d: record kind %d" % (b, kind))
         ch, cw = r[6], r[7]
         if not (0 < ch <= max_ch and cw > 0):
             raise ValueError("device_aug: sample %d: window %dx%d (max_ch %d)" % (b, ch, cw, max_ch))
-        inside(r[1], ch * cw * 3, blob_n, "image", b)
-        inside(r[2], ch * cw, blob_n, "label", b)
-        if r[3] >= 0 or r[4] >= 0 or r[5] >= 0:
-            inside(r[3], ch * cw * 3, blob_n, "paste image", b)
-            inside(r[4], ch * cw, blob_n, "paste label", b)
-            inside(r[5], 256, blob_n, "paste table", b)
+        if kind == AUG_KIND_STORE:
+            _aug_check_store_windows(r, b, store)
+            if r[3] >= 0 or r[4] >= 0 or r[5] >= 0:
+                inside(r[5], 256, blob_n, "paste table", b)
+        else:
+            inside(r[1], ch * cw * 3, blob_n, "image", b)
+            inside(r[2], ch * cw, blob_n, "label", b)
+            if r[3] >= 0 or r[4] >= 0 or r[5] >= 0:
+                inside(r[3], ch * cw * 3, blob_n, "paste image", b)
+                inside(r[4], ch * cw, blob_n, "paste label", b)
+                inside(r[5], 256, blob_n, "paste table", b)
         for (lo, n, k, taps, n_out, n_in, nm) in ((r[9], r[10], r[11], r[12], ow, cw, "horizontal"),
                                                   (r[13], r[14], r[15], r[16], oh, ch, "vertical")):
             if taps < 1:
@@ -769,10 +837,11 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch):
                     inside(off, oh * ow * 3, blob_n, "view %d FDA target" % k, b)
 
 
-def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch):
+def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch, store=None):
     """device tensors of one batch (blob uint8, tabs int32, recs int64 [B, 20]: include/hiast_hip.h, K15; ALREADY bounds-
     checked by the caller) -> (uint8 [B, oh, ow, 3], uint8 label [B, oh, ow]): CopyPaste select, flip, crop, Pillow's
-    two-pass 8-bit resample and the nearest label gather, byte for byte"""
+    two-pass 8-bit resample and the nearest label gather, byte for byte.  store: the uint8 buffer of device-resident
+    frames that records of kind 2 address (hiast_aug_geometry_store_u8)"""
     _req(blob, torch.uint8, 1, "blob")
     _req(tabs, torch.int32, 1, "tabs")
     _req(recs, torch.int64, 2, "recs")
@@ -781,6 +850,13 @@ def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch):
     tmp = torch.empty((B, max_ch, ow, 3), dtype=torch.uint8, device=dev)
     img = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=dev)
     lbl = torch.empty((B, oh, ow), dtype=torch.uint8, device=dev)
+    if store is not None:
+        _req(store, torch.uint8, 1, "store")
+        if store.device != dev or store.numel() == 0:
+            raise ValueError("aug_geometry_u8: the store must be a non-empty buffer on the batch's device")
+        check(_lib.load().hiast_aug_geometry_store_u8(_ptr(recs), _ptr(blob), _ptr(store), _ptr(tabs), _ptr(tmp), _ptr(img),
+                                                      _ptr(lbl), B, max_ch, oh, ow, _stream()), "hiast_aug_geometry_store_u8")
+        return img, lbl
     check(_lib.load().hiast_aug_geometry_u8(_ptr(recs), _ptr(blob), _ptr(tabs), _ptr(tmp), _ptr(img), _ptr(lbl), B, max_ch,
                                             oh, ow, _stream()), "hiast_aug_geometry_u8")
     return img, lbl
@@ -907,6 +983,19 @@ def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
     uint8 label [B, oh, ow]) on `device`: four uploads + one of the views' segments where a view has a colour launch, then
     geometry + per view the launch rounds of its segments (rows of level-1 ops: one round, the table launches only if a
     row equalises, one colour pass)"""
+    return _aug_batch(blob, tabs, recs, ops, oh, ow, max_ch, device, None)
+
+
+def aug_batch_store_u8(blob, tabs, recs, ops, oh, ow, max_ch, device, store):
+    """aug_batch_u8 for a batch that may hold records of kind 2: samples whose windows are read in place from `store`, the
+    device_store.ResidentSet of the batch's dataset (`buffer`: the frames on `device`, `frames`: the residency table on
+    the host).  Kinds 0, 1 and 2 may be mixed; the colour launches are those of aug_batch_u8"""
+    if store is None or not hasattr(store, "buffer") or not hasattr(store, "frames"):
+        raise ValueError("aug_batch_store_u8: a device store (buffer + residency table) is required")
+    return _aug_batch(blob, tabs, recs, ops, oh, ow, max_ch, device, store)
+
+
+def _aug_batch(blob, tabs, recs, ops, oh, ow, max_ch, device, store):
     for t, dt, nm in ((blob, torch.uint8, "blob"), (tabs, torch.int32, "tabs"), (recs, torch.int64, "recs"),
                       (ops, torch.int64, "ops")):
         if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != dt or not t.is_contiguous():
@@ -914,12 +1003,13 @@ def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
     if torch.device(device).type != "cuda":
         raise _lib.HiastLibraryError("the device-side sample path runs on the HIP device only")
     recs_h, ops_h = recs.numpy(), ops.numpy()
-    _aug_check_tables(blob.numel(), tabs.numpy(), recs_h, ops_h, oh, ow, max_ch)
+    _aug_check_tables(blob.numel(), tabs.numpy(), recs_h, ops_h, oh, ow, max_ch,
+                      None if store is None else (store.buffer.numel(), store.frames))
     up = lambda t: (t if t.is_pinned() else t.pin_memory()).to(device, non_blocking=True)      # noqa: E731
     blob_d, tabs_d, recs_d, ops_d = up(blob), up(tabs), up(recs), up(ops)
     segs_h, cuts = _aug_batch_segments(ops_h)              # (cut while the blob travels)
     segs_d = h2d_async(segs_h, device) if len(segs_h) else None
-    cur, lbl = aug_geometry_u8(blob_d, tabs_d, recs_d, oh, ow, max_ch)
+    cur, lbl = aug_geometry_u8(blob_d, tabs_d, recs_d, oh, ow, max_ch, None if store is None else store.buffer)
     views = []
     for k, cut in enumerate(cuts):
         if cut is not None:

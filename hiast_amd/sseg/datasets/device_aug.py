@@ -10,6 +10,10 @@ drawing; resampling and recolouring run on the device (hiast_amd/csrc/sample_aug
                                                  record row per sample (offsets, not pointers: built without a device)
     assemble_device_batch(batch, device)      -> what utils.to_device_batch returns (normalised float32 CHW views, labels)
 
+With device-resident frames (device_store.py) a sample whose frame — and CopyPaste source frame — is resident carries no
+bytes at all: pack_store_sample -> {"plan", "raw": {"store": (index, paste index | -1), ...}}; its record is of
+KIND_STORE and addresses the windows in place in the store (assemble_device_batch(batch, device, store)).
+
 A view plan is {"ops": [...], "host": bool}; ops are ("geom", Geometry), ("lut", uint8[256]), ("gray",), ("equalize",)
 and ("host", name).  At level 1 ColorJitter, GaussianBlur and FDA have no device form (PIL's C HSV conversion, scipy's
 float64 correlate, an FFT): a sample whose plan holds one of them is run through augmentations.aug() by the worker as
@@ -612,10 +616,11 @@ def execute_plan_host(plan, img, lbl, paste=None, sliced=False):
 # one int64 record row per sample (offsets into the batch's uint8 blob / int32 table blob)
 R_KIND, R_IMG, R_LBL, R_PIMG, R_PLBL, R_PTAB, R_CH, R_CW, R_FLIP, R_HLO, R_HN, R_HK, R_HT, R_VLO, R_VN, R_VK, R_VT, R_NX, \
     R_NY = range(19)
+R_STRIDE = 19                # KIND_STORE: the frame's width in pixels, the row stride of a window read in place
 REC_WORDS = 20
 # per (view, sample): kind, offset of the finished view, n ops, then (type, blob offset of the table) x MAX_OPS
 OPS_WORDS = 4 + 2 * MAX_OPS
-KIND_PLAN, KIND_FINISHED = 0, 1
+KIND_PLAN, KIND_FINISHED, KIND_STORE = 0, 1, 2
 
 
 def _align(n, a=16):
@@ -644,15 +649,35 @@ def pack_sample(plan, raw_img, raw_lbl, paste=None):
     """what a worker returns for a planned sample: {"plan", "raw"} with the slices of plan_window(plan); the reference
     image of every FDA op is decoded and resized to the view here, in the worker (raw["fda"], in op order)"""
     raw = {"img": torch.from_numpy(np.ascontiguousarray(raw_img)), "lbl": torch.from_numpy(np.ascontiguousarray(raw_lbl))}
+    _add_fda_views(raw, plan)
+    if paste is not None:
+        raw["paste_img"] = torch.from_numpy(np.ascontiguousarray(paste[0]))
+        raw["paste_lbl"] = torch.from_numpy(np.ascontiguousarray(paste[1]))
+        raw["paste_table"] = torch.from_numpy(np.ascontiguousarray(paste[2], np.uint8))
+    return {"raw": raw, "plan": plan}
+
+
+def _add_fda_views(raw, plan):
     out_shape = plan[0]["ops"][0][1].out
     fda = [torch.from_numpy(fda_target(op[1], out_shape, v.get("readers", {}).get(op[1])))
            for v in plan for op in v["ops"] if op[0] == "fda"]
     if fda:
         raw["fda"] = fda
+
+
+def pack_store_sample(plan, index, row, paste=None):
+    """what a worker returns for a planned sample whose frame is resident in the device store: no frame bytes.  index /
+    row: the frame's dataset index and its row of the residency table (image offset, label offset, H, W);
+    paste = (source index, its row, uint8[256] table) of CopyPaste.run_plan_index with a resident source of the frame's
+    shape.  The FDA target views are decoded and resized here, in the worker, as in pack_sample."""
+    rows = torch.full((2, 4), -1, dtype=torch.int64)
+    rows[0] = torch.as_tensor(row, dtype=torch.int64)
+    raw = {"store": (int(index), -1), "store_rows": rows}
     if paste is not None:
-        raw["paste_img"] = torch.from_numpy(np.ascontiguousarray(paste[0]))
-        raw["paste_lbl"] = torch.from_numpy(np.ascontiguousarray(paste[1]))
+        raw["store"] = (int(index), int(paste[0]))
+        rows[1] = torch.as_tensor(paste[1], dtype=torch.int64)
         raw["paste_table"] = torch.from_numpy(np.ascontiguousarray(paste[2], np.uint8))
+    _add_fda_views(raw, plan)
     return {"raw": raw, "plan": plan}
 
 
@@ -681,6 +706,7 @@ def build_batch_tables(samples):
             raise ValueError("device_aug batch: samples of different output size / view count (%s x%d vs %s x%d)"
                              % (shp, v, out, n_views))
     ops = np.zeros((n_views, B, OPS_WORDS), np.int64)
+    store_idx = np.full((B, 2), -1, np.int64)
     max_ch = 1
     for b, s in enumerate(samples):
         raw, r = s["raw"], recs[b]
@@ -693,13 +719,27 @@ def build_batch_tables(samples):
             continue
         g = s["plan"][0]["ops"][0][1]
         ch, cw = g.src[1] - g.src[0], g.src[3] - g.src[2]
-        if tuple(raw["img"].shape) != (ch, cw, 3) or tuple(raw["lbl"].shape) != (ch, cw):
-            raise ValueError("device_aug: raw slices %s do not match the plan's window %s" % (tuple(raw["img"].shape), g.src))
-        r[R_KIND], r[R_CH], r[R_CW], r[R_FLIP] = KIND_PLAN, ch, cw, int(g.flip)
-        r[R_IMG], r[R_LBL] = blob.add(raw["img"].numpy()), blob.add(raw["lbl"].numpy())
-        if "paste_img" in raw:
-            r[R_PIMG], r[R_PLBL] = blob.add(raw["paste_img"].numpy()), blob.add(raw["paste_lbl"].numpy())
-            r[R_PTAB] = blob.add(raw["paste_table"].numpy())
+        if "store" in raw:                   # the windows stay where they are: offsets of their first pixels in the store
+            (io, lo, fh, fw), (pio, plo, ph, pw) = raw["store_rows"].tolist()
+            first = g.src[0] * fw + g.src[2]
+            if io < 0 or lo < 0 or g.src[1] > fh or g.src[3] > fw:
+                raise ValueError("device_aug: window %s of a resident frame of %dx%d at %d" % (g.src, fh, fw, io))
+            r[R_KIND], r[R_CH], r[R_CW], r[R_FLIP], r[R_STRIDE] = KIND_STORE, ch, cw, int(g.flip), fw
+            r[R_IMG], r[R_LBL] = io + first * 3, lo + first
+            if raw["store"][1] >= 0:
+                if pio < 0 or plo < 0 or (ph, pw) != (fh, fw):
+                    raise ValueError("device_aug: paste source of %dx%d at %d for a frame of %dx%d" % (ph, pw, pio, fh, fw))
+                r[R_PIMG], r[R_PLBL], r[R_PTAB] = pio + first * 3, plo + first, blob.add(raw["paste_table"].numpy())
+            store_idx[b] = raw["store"]
+        else:
+            if tuple(raw["img"].shape) != (ch, cw, 3) or tuple(raw["lbl"].shape) != (ch, cw):
+                raise ValueError("device_aug: raw slices %s do not match the plan's window %s"
+                                 % (tuple(raw["img"].shape), g.src))
+            r[R_KIND], r[R_CH], r[R_CW], r[R_FLIP] = KIND_PLAN, ch, cw, int(g.flip)
+            r[R_IMG], r[R_LBL] = blob.add(raw["img"].numpy()), blob.add(raw["lbl"].numpy())
+            if "paste_img" in raw:
+                r[R_PIMG], r[R_PLBL] = blob.add(raw["paste_img"].numpy()), blob.add(raw["paste_lbl"].numpy())
+                r[R_PTAB] = blob.add(raw["paste_table"].numpy())
         r[R_HLO], r[R_HN], r[R_HK], r[R_HT] = tabs.add(g.hlo), tabs.add(g.hn), tabs.add(g.hk), g.hk.shape[1]
         r[R_VLO], r[R_VN], r[R_VK], r[R_VT] = tabs.add(g.vlo), tabs.add(g.vn), tabs.add(g.vk), g.vk.shape[1]
         r[R_NX], r[R_NY] = tabs.add(g.nx), tabs.add(g.ny)
@@ -732,9 +772,12 @@ def build_batch_tables(samples):
                 else:
                     raise ValueError("op %r has no device form" % (op[0],))
                 row[2] = i + 1
-    return {"blob": torch.from_numpy(blob.join()), "tabs": torch.from_numpy(tabs.join()),
-            "recs": torch.from_numpy(recs), "ops": torch.from_numpy(ops),
-            "meta": torch.tensor([n_views, out[0], out[1], max_ch, int(multi)], dtype=torch.int64)}
+    t = {"blob": torch.from_numpy(blob.join()), "tabs": torch.from_numpy(tabs.join()),
+         "recs": torch.from_numpy(recs), "ops": torch.from_numpy(ops),
+         "meta": torch.tensor([n_views, out[0], out[1], max_ch, int(multi)], dtype=torch.int64)}
+    if (store_idx[:, 0] >= 0).any():         # (frame index, paste source index | -1) of the KIND_STORE samples, -1 elsewhere
+        t["store_idx"] = torch.from_numpy(store_idx)
+    return t
 
 
 def collate(samples):
@@ -742,8 +785,15 @@ def collate(samples):
     differ in size, nothing is stacked); every other key collates as usual"""
     from torch.utils.data import default_collate
     rest = [{k: v for k, v in s.items() if k not in ("raw", "plan", "multi")} for s in samples]
+    # a sample over resident frames has no source label to cut its copy_paste_mask from (None): the masks of such a batch
+    # travel one by one and assemble_device_batch builds the missing ones on the device
+    masks = [r["copy_paste_mask"] for r in rest] if any(r.get("copy_paste_mask", 0) is None for r in rest) else None
+    if masks is not None:
+        rest = [{k: v for k, v in r.items() if k != "copy_paste_mask"} for r in rest]
     out = default_collate(rest)
     out["device_aug"] = build_batch_tables(samples)
+    if masks is not None:
+        out["device_aug"]["cp_masks"] = masks
     return out
 
 
@@ -751,14 +801,47 @@ def is_device_aug_batch(batch):
     return isinstance(batch, dict) and "device_aug" in batch
 
 
-def assemble_device_batch(batch, device):
+def _store_copy_paste_mask(t, store, device):
+    """the batch's copy_paste_mask [B, H, W] uint8 ON THE DEVICE, the bytes the worker path delivers: a worker's mask where
+    it made one, else where(table[lbl_src], lbl_src, 255) from the resident source label (255 everywhere without a source)"""
+    masks, idx = t["cp_masks"], t["store_idx"].tolist()
+    shapes = {tuple(m.shape) if m is not None else tuple(int(v) for v in store.frames[idx[b][0], 2:])
+              for b, m in enumerate(masks)}
+    if len(shapes) != 1:
+        raise ValueError("device_aug: copy_paste_mask of frames of different sizes in one batch: %s" % sorted(shapes))
+    out = torch.empty((len(masks),) + shapes.pop(), dtype=torch.uint8, device=device)
+    blob = None
+    for b, m in enumerate(masks):
+        if m is not None:
+            out[b].copy_(m, non_blocking=True)
+        elif idx[b][1] < 0:
+            out[b].fill_(255)
+        else:
+            if blob is None:
+                blob = t["blob"].to(device, non_blocking=True)
+            ptab = int(t["recs"][b, R_PTAB])
+            src = store.label(idx[b][1])
+            out[b] = torch.where(blob[ptab:ptab + 256][src.long()] != 0, src, torch.full_like(src, 255))
+    return out
+
+
+def assemble_device_batch(batch, device, store=None):
     """a collated device_aug batch -> what utils.to_device_batch returns for the same samples: normalised float32 CHW
-    views (a list for a multi-view dataset) and uint8 labels (a list of the same tensor per view)"""
+    views (a list for a multi-view dataset) and uint8 labels (a list of the same tensor per view).  store: the
+    device_store.ResidentSet of the batch's dataset, needed when the batch holds KIND_STORE samples; their part of
+    batch["copy_paste_mask"] is built here, on the device (the tensor then lives there)"""
     from hiast_amd import kernels as K
     from hiast_amd.sseg.datasets.utils import MEAN, STD
     t = batch["device_aug"]
     n_views, oh, ow, max_ch, multi = (int(v) for v in t["meta"])
-    views, lbl = K.aug_batch_u8(t["blob"], t["tabs"], t["recs"], t["ops"], oh, ow, max_ch, device)
+    if "store_idx" in t:
+        if store is None:
+            raise ValueError("device_aug: the batch holds samples over device-resident frames but no store was given")
+        views, lbl = K.aug_batch_store_u8(t["blob"], t["tabs"], t["recs"], t["ops"], oh, ow, max_ch, device, store)
+        if "cp_masks" in t:
+            batch["copy_paste_mask"] = _store_copy_paste_mask(t, store, device)
+    else:
+        views, lbl = K.aug_batch_u8(t["blob"], t["tabs"], t["recs"], t["ops"], oh, ow, max_ch, device)
     imgs = [K.normalize_u8(v, MEAN, STD) for v in views]
     if multi:
         return imgs, [lbl for _ in imgs]

@@ -99,7 +99,48 @@ class BaseDataset(Dataset):
             out["copy_paste_mask"] = torch.from_numpy(cp_mask)
         return out
 
+    def _store_item(self, index, seed, paste):
+        """the sample as a plan over device-resident frames (device_store.py: `store_table`, attached by the trainer's
+        loader), nothing loaded, or None: the frame or the CopyPaste source is not resident, the source has another shape
+        (it would need CopyPaste.resize), or the plan needs the host.  The draws are those of _device_aug_item from the same
+        generators in the same order; before None is returned `random` and `np.random` are put back as they were found,
+        so the caller's bytes path spends them once."""
+        import random
+        table = getattr(self, "store_table", None)
+        if table is None or not self._device_aug_on() or not 0 <= index < len(table) or int(table[index, 0]) < 0:
+            return None
+        row = table[index].tolist()
+        state, np_state = random.getstate(), (np.random.get_state() if paste else None)
+        if seed is not None:
+            random.seed(seed)
+        plan = device_aug.plan_sample(self.aug_fun, (row[2], row[3]), level=int(getattr(self, "device_aug_level", 1)))
+        ok, src = not device_aug.needs_host(plan), None
+        if ok and paste:
+            p_index, p_table = self.preprocessor.run_plan_index()
+            if p_index is not None:
+                p_row = table[p_index].tolist()
+                ok = self.preprocessor.dataset_copy_from is self and p_row[0] >= 0 and p_row[2:] == row[2:]
+                src = (p_index, p_row, p_table)
+        if not ok:
+            random.setstate(state)
+            if paste:
+                np.random.set_state(np_state)
+            return None
+        out = device_aug.pack_store_sample(plan, index, row, src)
+        out["image_paths"] = self.img_path_list[index]
+        if paste:
+            out["copy_paste_mask"] = None       # cut from the resident source label on the device (assemble_device_batch)
+        return out
+
+    def frame_shape(self, index):
+        """(H, W) of what load_data(index) returns, from the image's header alone (load_data resizes the label to the image)"""
+        with Image.open(self.img_path_list[index]) as im:
+            return im.size[1], im.size[0]
+
     def original_get_item(self, index):
+        out = self._store_item(index, index, False)
+        if out is not None:
+            return out
         (img, lbl, path), index = self._safe_load(index)
         if self._device_aug_on():
             return self._device_aug_item(img, lbl, path, index, False)
@@ -108,6 +149,9 @@ class BaseDataset(Dataset):
         return {"images": img, "labels": lbl, "image_paths": path}
 
     def get_item_with_copy_paste(self, index):
+        out = self._store_item(index, None, True)
+        if out is not None:
+            return out
         (img, lbl, path), index = self._safe_load(index)
         if self._device_aug_on():
             return self._device_aug_item(img, lbl, path, None, True)

@@ -76,6 +76,20 @@ class CopyPaste:
         np.copyto(mask, lbl_, where=table[lbl_] != 0)
         return (img_, lbl_, table), mask
 
+    def run_plan_index(self):
+        """run_plan() for device-resident frames (device_store.py): the same np.random draws, but the source stays where it
+        is — -> (dataset index of the source image in dataset_copy_from, uint8[256] table) or (None, None).  Nothing is
+        decoded: the caller addresses the source in the store, or restores the generators and takes run_plan()."""
+        if self.cfg.preprocessor.copy_paste.mode != "original":
+            raise NotImplementedError("copy_paste.mode %r" % self.cfg.preprocessor.copy_paste.mode)
+        c = self.random_select(self.hard_classes)
+        if c is None:
+            return None, None
+        name = np.random.choice(self.samples_with_class[c])
+        table = np.zeros(256, dtype=np.uint8)
+        table[np.asarray(self.hard_classes, dtype=np.int64)] = 1
+        return self.dataset_copy_from.get_file_to_idx(name), table
+
     def random_select(self, selected_classes):
         """rejection-sample a hard class (preprocessor.py:70-77).  Deviations: a class that no pseudo-labelled
         image contains is rejected too (the reference would raise in np.random.choice on its empty file list), and

@@ -70,17 +70,19 @@ def to_device_batch(images, labels, device):
     return imgs, lbls
 
 
-def assemble_device_batch(batch, device):
+def assemble_device_batch(batch, device, store=None):
     """a batch collated by a device_aug dataset (plans + raw bytes, device_aug.collate) -> what to_device_batch returns for
-    the same samples read without device_aug, bit for bit: the device executes the plans (hiast_aug_*_u8) and normalises"""
+    the same samples read without device_aug, bit for bit: the device executes the plans (hiast_aug_*_u8) and normalises.
+    store: the resident frames of the batch's dataset (device_store.ResidentSet; the trainer's store_of(dataset)) where
+    samples travel as plans over them"""
     from hiast_amd.sseg.datasets import device_aug
-    return device_aug.assemble_device_batch(batch, device)
+    return device_aug.assemble_device_batch(batch, device, store)
 
 
-def batch_to_device(batch, device):
+def batch_to_device(batch, device, store=None):
     """one DataLoader batch (dict) -> (images, labels) on the device, whichever way its dataset hands samples over"""
     if "device_aug" in batch:
-        return assemble_device_batch(batch, device)
+        return assemble_device_batch(batch, device, store)
     return to_device_batch(batch["images"], batch["labels"], device)
 
 

@@ -11,7 +11,19 @@ SWITCHES = {n: os.environ.get(n, "0") == "1" for n in _NAMES}
 # opt-IN paths (off unless set to "1"), kept apart from the opt-outs above; read once and flipped by tests the same way
 _OPT_IN_NAMES = ("HIAST_DISC_HIP", "HIAST_DISC_HIP_16BIT")
 OPT_IN = {n: os.environ.get(n, "0") == "1" for n in _OPT_IN_NAMES}
+# opt-in SIZES (0 = off), read once and flipped by tests the same way.  HIAST_DEVICE_STORE_GB: GB of device memory per process
+# for decoded frames that stay resident (sseg/datasets/device_store.py); overrides cfg.dataset.device_store_gb when > 0
+_SIZE_NAMES = ("HIAST_DEVICE_STORE_GB",)
+SIZES = {n: float(os.environ.get(n, "0") or 0) for n in _SIZE_NAMES}
 
 
 def on(name):
     return OPT_IN[name] if name in OPT_IN else SWITCHES[name]
+
+
+def device_store_bytes(cfg):
+    """the budget of the device store in bytes: HIAST_DEVICE_STORE_GB if > 0, else cfg.dataset.device_store_gb; 0 = off"""
+    gb = SIZES["HIAST_DEVICE_STORE_GB"]
+    if not gb > 0:
+        gb = float(getattr(cfg.dataset, "device_store_gb", 0) or 0)
+    return int(gb * (1 << 30)) if gb > 0 else 0

@@ -133,6 +133,7 @@ dataset:
   decoded_cache_gb: 16.0
   device_aug: false               # (not in the reference) workers plan, the device crops / resamples / recolours (device_aug.py)
   device_aug_level: 1             # with device_aug: 2 = ColorJitter and GaussianBlur run on the device too (1: those samples come finished from the workers); 3 = 2 + FDA (sparse-DFT form)
+  device_store_gb: 0.0            # (not in the reference) > 0: decoded frames stay in device memory up to this budget per process (validation set, then target, then source: device_store.py); training loaders use it only with device_aug
   source: {type: null, json_path: null, image_dir: null, aug_type: []}
   target: {type: null, json_path: null, image_dir: null, pseudo_dir: null, aug_type: []}
   val: {type: null, json_path: null, image_dir: null, resize_size: null}

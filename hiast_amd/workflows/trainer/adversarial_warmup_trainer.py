@@ -34,6 +34,6 @@ class AdversarialWarmupTrainer(BaseTrainer):
     def train(self):
         s = self.next_source_batch()
         t = self.next_target_batch()
-        s_img, s_lbl = du.batch_to_device(s, self.device)
-        t_img, _ = du.batch_to_device(t, self.device)
+        s_img, s_lbl = du.batch_to_device(s, self.device, self.store_of("s_dataset"))
+        t_img, _ = du.batch_to_device(t, self.device, self.store_of("t_dataset"))
         return self.train_on(s_img, s_lbl, t_img)

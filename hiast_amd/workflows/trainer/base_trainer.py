@@ -10,6 +10,7 @@ import torch
 import torch.distributed as dist
 
 from hiast_amd import functional as HF
+from hiast_amd import switches as SW
 from torch.nn.parallel import DistributedDataParallel as DDP
 from torch.utils.data import DataLoader, DistributedSampler
 
@@ -49,6 +50,25 @@ def _worker_init(_worker_id):
         os.nice(10)
     except OSError:
         pass
+
+
+def _sample_path(cfg, ds, shuffle, drop_last):
+    """how `ds` hands its samples over (attributes of the dataset, read by its __getitem__ in the workers)"""
+    # workers hand over uint8 images / labels; ToTensor + Normalize run on the device (same bits, 4-8x fewer bytes
+    # through the worker pipes and PCIe).  HIAST_HOST_TRANSFORM=1 keeps the reference's float32 / int64 batches.
+    ds.device_transform = os.environ.get("HIAST_HOST_TRANSFORM", "0") != "1"
+    # cfg.dataset.device_aug / HIAST_DEVICE_AUG=1 (training loaders only; off by default): workers draw every random
+    # decision and hand over the crop window's bytes + the plan, the device resamples and recolours (device_aug.py)
+    # cfg.dataset.device_aug_level: 2 / HIAST_DEVICE_AUG=2: ColorJitter and GaussianBlur are planned and run on the
+    # device too (no 'CCA' / 'SCA' sample falls back to the worker path)
+    # cfg.dataset.device_aug_level: 3 / HIAST_DEVICE_AUG=3: level 2 + FDA in its sparse-DFT form (no 'FDA-*' sample
+    # falls back unless geometry follows the FDA)
+    env = os.environ.get("HIAST_DEVICE_AUG", "0")
+    ds.device_aug = (ds.device_transform and shuffle and drop_last
+                     and (bool(getattr(cfg.dataset, "device_aug", False)) or env in ("1", "2", "3")))
+    ds.device_aug_level = int(env) if env in ("2", "3") else int(getattr(cfg.dataset, "device_aug_level", 1))
+    if ds.device_aug_level not in (1, 2, 3):
+        raise ValueError("dataset.device_aug_level is 1, 2 or 3, not %r" % (ds.device_aug_level,))
 
 
 class _EpochChain(torch.utils.data.Sampler):
@@ -95,6 +115,9 @@ class BaseTrainer:
     # with two uses of a weight autograd sums the two tensors on the MAIN stream while the side stream may still be
     # writing them.  Trainers that run the segmentation net more than once per step switch it off.
     wgrad_overlap = True
+    # cfg.dataset.device_store_gb / HIAST_DEVICE_STORE_GB > 0: the process's DeviceStore of decoded frames (sseg/datasets/
+    # device_store.py), created when the first loader is built; None = off
+    device_store = None
 
     def __init__(self, cfg, gpu_index):
         self.cfg = cfg
@@ -160,25 +183,38 @@ class BaseTrainer:
         self.model_recorder = ResultRecorder(self.cfg, self.gpu_index, self.g_optimizer, self.d_optimizer, "model",
                                              self.logger)
 
+    def _store_place(self, ds, shuffle, drop_last):
+        """cfg.dataset.device_store_gb / HIAST_DEVICE_STORE_GB > 0 (off by default): decode `ds` into the device store, as far
+        as the process's one budget goes, and attach the residency table to it — before its loader, and so its loader's
+        first iterator, exists: persistent workers see the table, which does not change afterwards.  A training set takes
+        part only with device_aug (its samples then travel as plans over the resident frames), the validation set always;
+        the validation set is placed first (small, and read by the student and the EMA model), then the sets in the order
+        of the calls (build_train_data_reader: target, then source).  -> the dataset's ResidentSet | None"""
+        _sample_path(self.cfg, ds, shuffle, drop_last)
+        budget = SW.device_store_bytes(self.cfg)
+        training = shuffle and drop_last
+        if budget <= 0 or (training and not ds.device_aug):
+            return None
+        if self.device_store is None:
+            from hiast_amd.sseg.datasets.device_store import DeviceStore
+            self.device_store = DeviceStore(self.device, budget)
+        if training and self._val_dataset() is not None:
+            self._store_place(self._val_dataset(), False, False)
+        return self.device_store.place(ds, self.cfg.dataset.num_workers)
+
+    def store_of(self, name):
+        """the resident frames of the dataset self.<name> (device_store.ResidentSet) | None: what batch_to_device /
+        assemble_device_batch are given with that dataset's batches"""
+        ds = getattr(self, name, None)
+        return self.device_store.of(ds) if self.device_store is not None and ds is not None else None
+
     def _loader(self, ds, batch_size, shuffle, drop_last):
-        # workers hand over uint8 images / labels; ToTensor + Normalize run on the device (same bits, 4-8x fewer bytes
-        # through the worker pipes and PCIe).  HIAST_HOST_TRANSFORM=1 keeps the reference's float32 / int64 batches.
-        ds.device_transform = os.environ.get("HIAST_HOST_TRANSFORM", "0") != "1"
+        _sample_path(self.cfg, ds, shuffle, drop_last)
+        if SW.device_store_bytes(self.cfg) > 0:
+            self._store_place(ds, shuffle, drop_last)
         sampler = DistributedSampler(ds, num_replicas=self.world, rank=self.gpu_index, shuffle=shuffle)
         nw = self.cfg.dataset.num_workers
         kw = dict(num_workers=nw, pin_memory=True, persistent_workers=nw > 0, worker_init_fn=_worker_init if nw > 0 else None)
-        # cfg.dataset.device_aug / HIAST_DEVICE_AUG=1 (training loaders only; off by default): workers draw every random
-        # decision and hand over the crop window's bytes + the plan, the device resamples and recolours (device_aug.py)
-        # cfg.dataset.device_aug_level: 2 / HIAST_DEVICE_AUG=2: ColorJitter and GaussianBlur are planned and run on the
-        # device too (no 'CCA' / 'SCA' sample falls back to the worker path)
-        # cfg.dataset.device_aug_level: 3 / HIAST_DEVICE_AUG=3: level 2 + FDA in its sparse-DFT form (no 'FDA-*' sample
-        # falls back unless geometry follows the FDA)
-        env = os.environ.get("HIAST_DEVICE_AUG", "0")
-        ds.device_aug = (ds.device_transform and shuffle and drop_last
-                         and (bool(getattr(self.cfg.dataset, "device_aug", False)) or env in ("1", "2", "3")))
-        ds.device_aug_level = int(env) if env in ("2", "3") else int(getattr(self.cfg.dataset, "device_aug_level", 1))
-        if ds.device_aug_level not in (1, 2, 3):
-            raise ValueError("dataset.device_aug_level is 1, 2 or 3, not %r" % (ds.device_aug_level,))
         if ds.device_aug:
             from hiast_amd.sseg.datasets import device_aug
             kw["collate_fn"] = device_aug.collate
@@ -192,21 +228,63 @@ class BaseTrainer:
         if s.type is not None and s.json_path is not None and s.image_dir is not None:
             self.s_dataset = DATASET[s.type](self.cfg, s.json_path, s.image_dir, aug_type=s.aug_type,
                                              num_classes=self.cfg.dataset.num_classes)
-            self.s_sampler, self.s_loader = self._loader(self.s_dataset, self.cfg.train.batch_size, True, True)
-            self.s_iter = iter(self.s_loader)
         t = self.cfg.dataset.target
         if t.type is not None and t.json_path and t.image_dir is not None:
             self.t_dataset = DATASET[t.type](self.cfg, t.json_path, t.image_dir, pseudo_dir=t.pseudo_dir,
                                              aug_type=t.aug_type, num_classes=self.cfg.dataset.num_classes)
+            self._store_place(self.t_dataset, True, True)       # (the store's budget goes to the target set before the source set)
+        if getattr(self, "s_dataset", None) is not None:
+            self.s_sampler, self.s_loader = self._loader(self.s_dataset, self.cfg.train.batch_size, True, True)
+            self.s_iter = iter(self.s_loader)
+        if getattr(self, "t_dataset", None) is not None:
             self.t_sampler, self.t_loader = self._loader(self.t_dataset, self.cfg.train.batch_size, True, True)
             self.t_iter = iter(self.t_loader)
 
+    def _val_dataset(self):
+        """the validation set | None, built once (the device store places it before the training sets)"""
+        if "_v_dataset" not in self.__dict__:
+            v = self.cfg.dataset.val
+            self._v_dataset = None
+            if v.type is not None and v.json_path and v.image_dir is not None:
+                self._v_dataset = DATASET[v.type](self.cfg, v.json_path, v.image_dir, num_classes=self.cfg.dataset.num_classes)
+        return self._v_dataset
+
     def build_val_data_reader(self):
-        v = self.cfg.dataset.val
-        self.v_loader = None
-        if v.type is not None and v.json_path and v.image_dir is not None:
-            ds = DATASET[v.type](self.cfg, v.json_path, v.image_dir, num_classes=self.cfg.dataset.num_classes)
-            _, self.v_loader = self._loader(ds, self.cfg.train.batch_size, False, False)
+        self.v_loader = self.v_resident = None
+        ds = self._val_dataset()
+        if ds is not None:
+            sampler, self.v_loader = self._loader(ds, self.cfg.train.batch_size, False, False)
+            self.v_resident = self._val_store_batches(ds, sampler)
+
+    def _val_store_batches(self, ds, sampler):
+        """validation from the device store: (ResidentSet, [(dataset indices, H, W) per batch]) in the loader's order — the
+        sampler's indices cut into batches of the trainer's size, the ragged last one included — or None, and validation reads
+        the loader as a whole: no store, a set that is not resident frame for frame, frames of unequal size in one batch,
+        or a validation set with augmentations"""
+        rs = self.store_of("_v_dataset")
+        if rs is None or not rs.all_resident() or ds.aug_fun is not None:
+            return None
+        idx, bs = list(sampler), self.cfg.train.batch_size
+        batches = []
+        for i in range(0, len(idx), bs):
+            shapes = {(int(rs.frames[j, 2]), int(rs.frames[j, 3])) for j in idx[i:i + bs]}
+            if len(shapes) != 1:
+                return None
+            batches.append((idx[i:i + bs],) + shapes.pop())
+        return rs, batches
+
+    def _val_batches(self):
+        """(normalised images, labels) of the validation set on the device, batch by batch: from the device store when the
+        whole set is resident (the same bits as the loader's batches, self.v_loader is not touched), else from the loader"""
+        from hiast_amd import kernels as K
+        if getattr(self, "v_resident", None) is not None:
+            rs, batches = self.v_resident
+            for idx, h, w in batches:
+                img = K.normalize_gather_u8(rs.buffer, torch.from_numpy(rs.frames[idx, 0].copy()), h, w, du.MEAN, du.STD)
+                yield img, torch.stack([rs.label(j) for j in idx])
+            return
+        for data in self.v_loader:
+            yield du.to_device_batch(data["images"], data["labels"], self.device)
 
     def next_target_batch(self):
         try:
@@ -316,8 +394,7 @@ class BaseTrainer:
         model.eval()                 # the WRAPPER, like the reference (base_trainer.py:161): wrapper and net stay in step
         C = self.cfg.dataset.num_classes
         acc = torch.zeros(2, C, dtype=torch.int64, device=self.device)
-        for data in self.v_loader:
-            img, lbl = du.to_device_batch(data["images"], data["labels"], self.device)
+        for img, lbl in self._val_batches():
             size = self.cfg.dataset.val.resize_size or tuple(img.shape[2:])
             img = HF.upsample_bilinear_ac(img, size) if tuple(size) != tuple(img.shape[2:]) else img
             with torch.autocast("cuda", dtype=self.amp_dtype, enabled=self.amp_dtype is not None):

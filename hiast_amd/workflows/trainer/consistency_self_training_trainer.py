@@ -179,7 +179,7 @@ class ConsistencySelfTrainingTrainer(BaseTrainer):
     def train(self):
         t = self.next_target_batch()
         if "device_aug" in t:                   # cfg.dataset.device_aug: the device executes the workers' plans
-            img, plbl = du.assemble_device_batch(t, self.device)
+            img, plbl = du.assemble_device_batch(t, self.device, self.store_of("t_dataset"))
             if isinstance(img, (list, tuple)):
                 assert len(img) == 2 and plbl[0] is plbl[1]
                 weak, strong, plbl = img[0], img[1], plbl[0]

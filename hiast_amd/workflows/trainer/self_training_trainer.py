@@ -25,4 +25,4 @@ class SelfTrainingTrainer(BaseTrainer):
 
     def train(self):
         t = self.next_target_batch()
-        return self.train_on(*du.batch_to_device(t, self.device))
+        return self.train_on(*du.batch_to_device(t, self.device, self.store_of("t_dataset")))

@@ -22,4 +22,4 @@ class SourceOnlyTrainer(BaseTrainer):
 
     def train(self):
         s = self.next_source_batch()
-        return self.train_on(*du.batch_to_device(s, self.device))
+        return self.train_on(*du.batch_to_device(s, self.device, self.store_of("s_dataset")))

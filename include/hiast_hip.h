@@ -551,6 +551,28 @@ int hiast_normalize_u8(const uint8_t* img, float* out, int B, int64_t HW, const 
 int hiast_aug_geometry_u8(const int64_t* recs, const uint8_t* blob, const int32_t* tabs, uint8_t* tmp,
                           uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow, hiast_stream_t stream);
 
+/* ---- K15 with device-resident frames (cfg.dataset.device_store_gb; hiast_amd/sseg/datasets/device_store.py) ---------
+ * `store`: ONE uint8 device buffer of decoded frames (image [H][W][3] and label [H][W] each, every frame 16-byte
+ * aligned), addressed by 64-bit element offsets from its base.
+ * hiast_aug_geometry_store_u8: hiast_aug_geometry_u8 with a third record kind, HIAST_STORE_KIND (2): img / lbl
+ *   (and paste_img / paste_lbl, or -1) are offsets INTO THE STORE of the window's first pixel — frame offset +
+ *   (y1 * W + x1) * 3 for an image, + y1 * W + x1 for a label —, record word HIAST_STORE_REC_STRIDE (19, spare in the
+ *   other kinds) is the frame's width W in pixels = the row stride (>= cw); paste_table and every tap / nearest table
+ *   stay in blob / tabs.  The arithmetic is that of kind 0 (which reads the same window with row stride cw); kinds 0, 1
+ *   and 2 may be mixed in one batch.  hiast_aug_geometry_u8 itself knows kinds 0 and 1 only.
+ * hiast_normalize_gather_u8: hiast_normalize_u8 on B frames of HW pixels that start at store + offsets[b] (offsets:
+ *   DEVICE int64 [B]) -> out float32 [B][3][HW], one launch, the same operations in the same order (bit-identical to
+ *   hiast_normalize_u8 on the same bytes).  mean / std: HOST float[3].
+ * Both refuse a null pointer (HIAST_E_ARG) and the extents their neighbours refuse (HIAST_E_RANGE) before any launch;
+ * offsets are bounds-checked by the host wrappers (hiast_amd/kernels.py), table indices are clamped as in K15. */
+#define HIAST_STORE_KIND 2
+#define HIAST_STORE_REC_STRIDE 19
+int hiast_aug_geometry_store_u8(const int64_t* recs, const uint8_t* blob, const uint8_t* store, const int32_t* tabs,
+                                uint8_t* tmp, uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow,
+                                hiast_stream_t stream);
+int hiast_normalize_gather_u8(const uint8_t* store, const int64_t* offsets, float* out, int B, int64_t HW, const float* mean,
+                              const float* std, hiast_stream_t stream);
+
 /* ---- K15b: the colour ops of the device-side sample path, every level -------------------------------------------
  * Level 1: LUT, OpenCV's fixed-point gray, cv2.equalizeHist (per-channel histogram -> float64 table, rint).  Level 2
  * (cfg.dataset.device_aug_level: 2): ColorJitter and GaussianBlur as plan ops.  All byte-identical to

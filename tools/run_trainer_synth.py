@@ -4,10 +4,13 @@ on N synthetic Cityscapes-size (2048x1024) target images whose pseudo-labels wer
 processes -> H2D -> teacher forward, student forward/backward, Adam, EMA).  Prints images/s including the host data path
 next to the compute-only number bench.py reports.
     python tools/run_trainer_synth.py [N=32] [batch=8] [workers=14] [iters=24] [native_h=1024] [native_w=2048] [device_aug=0]
+                                      [store_gb=0]
 device_aug=1: cfg.dataset.device_aug — the workers plan, the device crops / resamples / recolours (DESIGN §5);
 device_aug=2: the same at cfg.dataset.device_aug_level 2 (ColorJitter and GaussianBlur on the device too);
 device_aug=3: level 3 (FDA on the device too; this tool's ['MS', 'CCA'] target list holds none — tools/bench_fda.py
-measures a ['MS', 'FDA-Target'] source set through the DataLoader at level 2 against level 3)."""
+measures a ['MS', 'FDA-Target'] source set through the DataLoader at level 2 against level 3).
+store_gb > 0 (with device_aug): cfg.dataset.device_store_gb — the decoded frames stay in device memory, samples travel as
+plans over them; the fill time and the bytes held are printed."""
 import os
 import shutil
 import sys
@@ -41,6 +44,7 @@ nh = int(sys.argv[5]) if len(sys.argv) > 5 else 1024
 nwid = int(sys.argv[6]) if len(sys.argv) > 6 else 2048
 aug_level = int(sys.argv[7]) if len(sys.argv) > 7 else 0
 assert aug_level in (0, 1, 2, 3), "device_aug is 0, 1, 2 or 3"
+store_gb = float(sys.argv[8]) if len(sys.argv) > 8 else 0.0
 dev_aug = aug_level > 0
 root = tempfile.mkdtemp(prefix="hiast_train_")
 try:
@@ -77,10 +81,17 @@ try:
     cfg.preprocessor.type = "CopyPaste"
     cfg.dataset.device_aug = dev_aug
     cfg.dataset.device_aug_level = max(aug_level, 1)
+    cfg.dataset.device_store_gb = store_gb
     TO_DEVICE = "assemble_device_batch" if dev_aug else "to_device_batch"     # the call of du that a batch goes through
     cfg.work_dir = os.path.join(root, "work")
     def measure(tag, warm=6):
+        t_build = time.time()
         tr = TRAINER[cfg.trainer](cfg, 0)
+        if tr.device_store is not None:
+            torch.cuda.synchronize()
+            print("  device store: %.1f MB held (%d of %d target frames resident); trainer built in %.1f s, the fill included"
+                  % (tr.device_store.bytes_held() / 1e6, int((tr.store_of("t_dataset").frames[:, 0] >= 0).sum()),
+                     len(tr.t_dataset), time.time() - t_build), flush=True)
         wait = [0.0]
         fetch = tr.next_target_batch
 
@@ -139,7 +150,9 @@ try:
             print("  breakdown (ms/iter): " + ", ".join("%s %.1f" % (k, v / iters * 1e3) for k, v in parts.items()), flush=True)
         del tr.next_target_batch                # (the instance attribute; the class method is back)
         print("ConsistencySelfTrainingTrainer end to end, %s (DataLoader, %d workers, CopyPaste + MS + CCA, bs %d, device_aug %s): "
-              "%.1f ms/iter = %.1f images/s" % (tag, nw, bs, "level %d" % aug_level if dev_aug else "off", dt * 1e3, bs / dt), flush=True)
+              "%.1f ms/iter = %.1f images/s" % (tag, nw, bs, ("level %d" % aug_level if dev_aug else "off")
+                                                + (", device store %g GB" % store_gb if store_gb > 0 else ""), dt * 1e3, bs / dt),
+              flush=True)
         # host data path alone: how fast can the workers deliver batches?
         t0 = time.time()
         for _ in range(iters):
