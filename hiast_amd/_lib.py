@@ -101,6 +101,9 @@ SIGNATURES = {
     "hiast_multi_copy": (c_int, [c_vp, c_int, c_vp]),
     "hiast_aug_geometry_u8": (c_int, [c_vp] * 6 + [c_int] * 4 + [c_vp]),
     "hiast_aug_geometry_store_u8": (c_int, [c_vp] * 7 + [c_int] * 4 + [c_vp]),
+    "hiast_aug_records_check": (c_int, [c_vp, c_vp, c_i64, c_int, c_int]),
+    "hiast_aug_geometry_mix_u8": (c_int, [c_vp] * 7 + [c_int] * 4 + [c_vp]),
+    "hiast_aug_paste_mask_u8": (c_int, [c_vp] * 4 + [c_int] * 3 + [c_vp]),
     "hiast_normalize_gather_u8": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp]),
     "hiast_aug2_table_u8":(c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),
     "hiast_aug2_colour_u8": (c_int, [c_vp] * 6 + [c_int, c_i64, c_vp]),

@@ -720,6 +720,10 @@ AUG_FDA_MAX_BORDER, AUG_FDA_BORDER_SHIFT, AUG_FDA_MIN_SIDE = 2, 40, 8
 
 
 AUG_KIND_STORE, AUG_REC_STRIDE = 2, 19                   # include/hiast_hip.h HIAST_STORE_KIND, HIAST_STORE_REC_STRIDE
+# a kind 0 / kind 2 record whose paste is confined to a rectangle: its paste table is followed by ry0, ry1, rx0, rx1 (int32,
+# window coordinates); include/hiast_hip.h HIAST_MIX_KIND_PLAN_RECT, HIAST_MIX_KIND_STORE_RECT, HIAST_MIX_TABLE_BYTES
+AUG_KIND_PLAN_RECT, AUG_KIND_STORE_RECT, AUG_MIX_TABLE_BYTES = 3, 4, 256 + 16
+AUG_RECT_KINDS = (AUG_KIND_PLAN_RECT, AUG_KIND_STORE_RECT)
 
 
 def _aug_check_store_windows(r, b, store):
@@ -751,10 +755,21 @@ def _aug_check_store_windows(r, b, store):
                              % (b, what, y1, x1, ch, cw, stride, fh, fw))
 
 
-def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch, store=None):
+def _aug_check_rect(blob, off, ch, cw, b):
+    """the rectangle behind the paste table of a record of kind 3 / 4 (blob: numpy uint8 | None) inside [0, ch] x [0, cw]"""
+    if blob is None:
+        raise ValueError("device_aug: sample %d: a record with a paste rectangle, but the blob's bytes are not given" % b)
+    y0, y1, x0, x1 = (int(v) for v in blob[off + 256:off + AUG_MIX_TABLE_BYTES].view("<i4"))
+    if not (0 <= y0 <= y1 <= ch and 0 <= x0 <= x1 <= cw):
+        raise ValueError("device_aug: sample %d: paste rectangle (%d, %d, %d, %d) outside its window of %dx%d"
+                         % (b, y0, y1, x0, x1, ch, cw))
+
+
+def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch, store=None, blob=None):
     """host-side bounds of a batch's record tables (numpy views of the HOST tensors): every offset + extent inside its
     blob, every table index inside the sample's window — a kernel that reads outside can take the node down.  store:
-    (bytes, residency table) of the device-resident frames that records of kind 2 address (_aug_check_store_windows)"""
+    (bytes, residency table) of the device-resident frames that records of kind 2 / 4 address (_aug_check_store_windows);
+    blob: the blob's bytes (numpy uint8 [blob_n]), needed when a record is of kind 3 / 4: its rectangle is read there"""
     def inside(off, n, size, what, b):
         if off < 0 or off % 4 != 0 or off + n > size:
             raise ValueError("device_aug: sample %d: %s [%d, +%d) outside its blob of %d" % (b, what, off, n, size))
@@ -771,22 +786,28 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch, store=None):
                     raise ValueError("device_aug: sample %d: view %d of a finished sample has kind %d" % (b, k, int(ops[k, b, 0])))
                 inside(int(ops[k, b, 1]), oh * ow * 3, blob_n, "finished view %d" % k, b)
             continue
-        if kind not in (0, AUG_KIND_STORE):
+        if kind not in (0, AUG_KIND_STORE) + AUG_RECT_KINDS:
             raise ValueError("device_aug: sample %d: record kind %d" % (b, kind))
         ch, cw = r[6], r[7]
         if not (0 < ch <= max_ch and cw > 0):
             raise ValueError("device_aug: sample %d: window %dx%d (max_ch %d)" % (b, ch, cw, max_ch))
-        if kind == AUG_KIND_STORE:
+        rect = kind in AUG_RECT_KINDS
+        tab_n = AUG_MIX_TABLE_BYTES if rect else 256
+        if rect and (r[3] < 0 or r[4] < 0 or r[5] < 0):
+            raise ValueError("device_aug: sample %d: record kind %d without a paste source" % (b, kind))
+        if kind in (AUG_KIND_STORE, AUG_KIND_STORE_RECT):
             _aug_check_store_windows(r, b, store)
             if r[3] >= 0 or r[4] >= 0 or r[5] >= 0:
-                inside(r[5], 256, blob_n, "paste table", b)
+                inside(r[5], tab_n, blob_n, "paste table", b)
         else:
             inside(r[1], ch * cw * 3, blob_n, "image", b)
             inside(r[2], ch * cw, blob_n, "label", b)
             if r[3] >= 0 or r[4] >= 0 or r[5] >= 0:
                 inside(r[3], ch * cw * 3, blob_n, "paste image", b)
                 inside(r[4], ch * cw, blob_n, "paste label", b)
-                inside(r[5], 256, blob_n, "paste table", b)
+                inside(r[5], tab_n, blob_n, "paste table", b)
+        if rect:
+            _aug_check_rect(blob, r[5], ch, cw, b)
         for (lo, n, k, taps, n_out, n_in, nm) in ((r[9], r[10], r[11], r[12], ow, cw, "horizontal"),
                                                   (r[13], r[14], r[15], r[16], oh, ch, "vertical")):
             if taps < 1:
@@ -837,14 +858,31 @@ def _aug_check_tables(blob_n, tabs, recs, ops, oh, ow, max_ch, store=None):
                     inside(off, oh * ow * 3, blob_n, "view %d FDA target" % k, b)
 
 
-def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch, store=None):
+def _aug_records_check(host, max_kind, entry):
+    """hiast_aug_records_check on the HOST copy of a batch's records, host = (recs int64 [B, 20], blob uint8) as contiguous
+    numpy arrays or host tensors: the record kinds the entry knows, and the rectangle of every record of kind 3 / 4"""
+    recs_h, blob_h = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a for a in host)
+    if any(not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != dt or t.dim() != nd or not t.is_contiguous()
+           for t, dt, nd in ((recs_h, torch.int64, 2), (blob_h, torch.uint8, 1))) or recs_h.shape[1] != AUG_REC_WORDS:
+        raise ValueError("%s: the host copies of recs [B, %d] and blob are required" % (entry, AUG_REC_WORDS))
+    rc = _lib.load().hiast_aug_records_check(_ptr(recs_h), _ptr(blob_h), blob_h.numel(), recs_h.shape[0], max_kind)
+    if rc != 0:                     # (a host-side check, no launch: reported under the entry it guards, and only when it refuses)
+        check(rc, entry)
+
+
+def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch, store=None, host=None):
     """device tensors of one batch (blob uint8, tabs int32, recs int64 [B, 20]: include/hiast_hip.h, K15; ALREADY bounds-
     checked by the caller) -> (uint8 [B, oh, ow, 3], uint8 label [B, oh, ow]): CopyPaste select, flip, crop, Pillow's
     two-pass 8-bit resample and the nearest label gather, byte for byte.  store: the uint8 buffer of device-resident
-    frames that records of kind 2 address (hiast_aug_geometry_store_u8)"""
+    frames that records of kind 2 address (hiast_aug_geometry_store_u8).  host: the host copies (recs, blob) — with them
+    a record kind these entries do not know (3, 4; 2 without a store) is refused with HIAST_E_ARG before anything is
+    allocated or launched"""
     _req(blob, torch.uint8, 1, "blob")
     _req(tabs, torch.int32, 1, "tabs")
     _req(recs, torch.int64, 2, "recs")
+    if host is not None:
+        _aug_records_check(host, 1 if store is None else AUG_KIND_STORE,
+                           "hiast_aug_geometry_u8" if store is None else "hiast_aug_geometry_store_u8")
     B = recs.shape[0]
     dev = blob.device
     tmp = torch.empty((B, max_ch, ow, 3), dtype=torch.uint8, device=dev)
@@ -860,6 +898,73 @@ def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch, store=None):
     check(_lib.load().hiast_aug_geometry_u8(_ptr(recs), _ptr(blob), _ptr(tabs), _ptr(tmp), _ptr(img), _ptr(lbl), B, max_ch,
                                             oh, ow, _stream()), "hiast_aug_geometry_u8")
     return img, lbl
+
+
+def aug_geometry_mix_u8(blob, tabs, recs, oh, ow, max_ch, store=None, host=None, out=None):
+    """aug_geometry_u8 for batches that may hold every record kind 0..4 (hiast_aug_geometry_mix_u8): kinds 3 and 4 confine
+    the paste to the rectangle behind their table (ClassMix has none, CutMix has one).  store may be None when no record
+    is of kind 2 or 4.  host: as for aug_geometry_u8 (kinds 0..4, and every rectangle inside its window).  out: (tmp, img,
+    lbl) to write into instead of fresh tensors (uint8, of B*max_ch*ow*3, B*oh*ow*3 and B*oh*ow elements)"""
+    _req(blob, torch.uint8, 1, "blob")
+    _req(tabs, torch.int32, 1, "tabs")
+    _req(recs, torch.int64, 2, "recs")
+    if host is not None:
+        _aug_records_check(host, AUG_KIND_STORE_RECT, "hiast_aug_geometry_mix_u8")
+    B = recs.shape[0]
+    dev = blob.device
+    if store is not None:
+        _req(store, torch.uint8, 1, "store")
+        if store.device != dev or store.numel() == 0:
+            raise ValueError("aug_geometry_mix_u8: the store must be a non-empty buffer on the batch's device")
+    if out is None:
+        tmp = torch.empty((B, max_ch, ow, 3), dtype=torch.uint8, device=dev)
+        img = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=dev)
+        lbl = torch.empty((B, oh, ow), dtype=torch.uint8, device=dev)
+    else:
+        tmp, img, lbl = out
+        for t, n, nm in ((tmp, B * max_ch * ow * 3, "tmp"), (img, B * oh * ow * 3, "img"), (lbl, B * oh * ow, "lbl")):
+            if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous() or t.numel() != n:
+                raise ValueError("aug_geometry_mix_u8: %s must be a contiguous uint8 tensor of %d elements on the batch's device"
+                                 % (nm, n))
+    check(_lib.load().hiast_aug_geometry_mix_u8(_ptr(recs), _ptr(blob), 0 if store is None else _ptr(store), _ptr(tabs),
+                                                _ptr(tmp), _ptr(img), _ptr(lbl), B, max_ch, oh, ow, _stream()),
+          "hiast_aug_geometry_mix_u8")
+    return img, lbl
+
+
+def paste_mask_u8(store, blob, prm, out):
+    """the copy_paste_mask of the frames out[prm[:, 6]] in ONE launch (hiast_aug_paste_mask_u8).  store: the uint8 buffer of
+    device-resident frames; blob: the batch's uint8 blob ON THE DEVICE; prm: HOST numpy int64 [n, 8] = (offset of the source
+    label in the store | -1, blob offset of the 256-byte table, y0, y1, x0, x1 in frame coordinates, frame of `out`, 0);
+    out: uint8 [B, H, W] on the device.  out[f] = where(table[src] & inside the rectangle, src, 255); -1: 255 everywhere.
+    Every offset, frame index and rectangle is checked here, before the launch"""
+    _req(store, torch.uint8, 1, "store")
+    _req(blob, torch.uint8, 1, "blob")
+    _req(out, torch.uint8, 3, "out")
+    prm = np.ascontiguousarray(prm, np.int64)
+    if prm.ndim != 2 or prm.shape[1] != 8 or prm.shape[0] < 1:
+        raise ValueError("paste_mask_u8: prm of shape %s (int64 [n, 8])" % (prm.shape,))
+    if store.device != out.device or blob.device != out.device or store.numel() == 0:
+        raise ValueError("paste_mask_u8: store, blob and out must lie on one device, the store non-empty")
+    Bo, H, W = out.shape
+    seen = set()
+    for i, (src, tab, y0, y1, x0, x1, f, _) in enumerate(prm.tolist()):
+        if not 0 <= f < Bo or f in seen:
+            raise ValueError("paste_mask_u8: row %d writes frame %d of %d (each frame at most once)" % (i, f, Bo))
+        seen.add(f)
+        if src == -1:
+            continue
+        if src < 0 or src + H * W > store.numel():
+            raise ValueError("paste_mask_u8: row %d: source label [%d, +%d) outside the store of %d" % (i, src, H * W, store.numel()))
+        if tab < 0 or tab + 256 > blob.numel():
+            raise ValueError("paste_mask_u8: row %d: table [%d, +256) outside the blob of %d" % (i, tab, blob.numel()))
+        if not (0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W):
+            raise ValueError("paste_mask_u8: row %d: rectangle (%d, %d, %d, %d) outside the frame of %dx%d"
+                             % (i, y0, y1, x0, x1, H, W))
+    prm_d = h2d_async(prm, out.device)
+    check(_lib.load().hiast_aug_paste_mask_u8(_ptr(prm_d), _ptr(store), _ptr(blob), _ptr(out), prm.shape[0], H, W, _stream()),
+          "hiast_aug_paste_mask_u8")
+    return out
 
 
 def _aug_segments(ops_view):
@@ -989,7 +1094,8 @@ def aug_batch_u8(blob, tabs, recs, ops, oh, ow, max_ch, device):
 def aug_batch_store_u8(blob, tabs, recs, ops, oh, ow, max_ch, device, store):
     """aug_batch_u8 for a batch that may hold records of kind 2: samples whose windows are read in place from `store`, the
     device_store.ResidentSet of the batch's dataset (`buffer`: the frames on `device`, `frames`: the residency table on
-    the host).  Kinds 0, 1 and 2 may be mixed; the colour launches are those of aug_batch_u8"""
+    the host).  Kinds 0, 1 and 2 (and 3, 4: a paste confined to a rectangle) may be mixed; the colour launches are those of
+    aug_batch_u8"""
     if store is None or not hasattr(store, "buffer") or not hasattr(store, "frames"):
         raise ValueError("aug_batch_store_u8: a device store (buffer + residency table) is required")
     return _aug_batch(blob, tabs, recs, ops, oh, ow, max_ch, device, store)
@@ -1004,12 +1110,14 @@ def _aug_batch(blob, tabs, recs, ops, oh, ow, max_ch, device, store):
         raise _lib.HiastLibraryError("the device-side sample path runs on the HIP device only")
     recs_h, ops_h = recs.numpy(), ops.numpy()
     _aug_check_tables(blob.numel(), tabs.numpy(), recs_h, ops_h, oh, ow, max_ch,
-                      None if store is None else (store.buffer.numel(), store.frames))
+                      None if store is None else (store.buffer.numel(), store.frames), blob.numpy())
+    mix = bool(np.isin(recs_h[:, 0], AUG_RECT_KINDS).any())       # a batch with a rectangle: the entry that knows kinds 3 and 4
     up = lambda t: (t if t.is_pinned() else t.pin_memory()).to(device, non_blocking=True)      # noqa: E731
     blob_d, tabs_d, recs_d, ops_d = up(blob), up(tabs), up(recs), up(ops)
     segs_h, cuts = _aug_batch_segments(ops_h)              # (cut while the blob travels)
     segs_d = h2d_async(segs_h, device) if len(segs_h) else None
-    cur, lbl = aug_geometry_u8(blob_d, tabs_d, recs_d, oh, ow, max_ch, None if store is None else store.buffer)
+    cur, lbl = (aug_geometry_mix_u8 if mix else aug_geometry_u8)(blob_d, tabs_d, recs_d, oh, ow, max_ch,
+                                                                 None if store is None else store.buffer, host=(recs, blob))
     views = []
     for k, cut in enumerate(cuts):
         if cut is not None:

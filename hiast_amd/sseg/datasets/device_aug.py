@@ -14,6 +14,10 @@ With device-resident frames (device_store.py) a sample whose frame — and CopyP
 bytes at all: pack_store_sample -> {"plan", "raw": {"store": (index, paste index | -1), ...}}; its record is of
 KIND_STORE and addresses the windows in place in the store (assemble_device_batch(batch, device, store)).
 
+A paste (CopyPaste, ClassMix, CutMix: preprocessor.py) is part of the plan: (source, source label, uint8[256] table[, rect]),
+rect = (y0, y1, x0, x1) in frame coordinates, half-open, absent / None = the whole frame.  A paste with a rectangle travels
+as a record of kind 3 (bytes) or 4 (store): the rectangle follows the table in the blob, in window coordinates.
+
 A view plan is {"ops": [...], "host": bool}; ops are ("geom", Geometry), ("lut", uint8[256]), ("gray",), ("equalize",)
 and ("host", name).  At level 1 ColorJitter, GaussianBlur and FDA have no device form (PIL's C HSV conversion, scipy's
 float64 correlate, an FFT): a sample whose plan holds one of them is run through augmentations.aug() by the worker as
@@ -382,12 +386,31 @@ def equalize_luts(img):
     return luts
 
 
+def paste_rect(paste):
+    """the rectangle (y0, y1, x0, x1; frame coordinates, half-open) of a paste tuple, or None = the whole frame"""
+    return None if paste is None or len(paste) < 4 or paste[3] is None else tuple(int(v) for v in paste[3])
+
+
+def window_rect(rect, src):
+    """a frame-coordinate rectangle in the coordinates of the window src = (y1, y2, x1, x2), clipped to it; an empty
+    intersection is (0, 0, 0, 0)"""
+    y0, y1 = (min(max(int(v) - src[0], 0), src[1] - src[0]) for v in rect[:2])
+    x0, x1 = (min(max(int(v) - src[2], 0), src[3] - src[2]) for v in rect[2:])
+    return (y0, y1, x0, x1) if y0 < y1 and x0 < x1 else (0, 0, 0, 0)
+
+
 def execute_geometry_host(g, raw_img, raw_lbl, paste=None):
-    """raw_img / raw_lbl: the slices g.src of the frame; paste = (src_img, src_lbl, table uint8[256]) over the same
-    slice: the CopyPaste composite, taken per pixel before resampling"""
+    """raw_img / raw_lbl: the slices g.src of the frame; paste = (src_img, src_lbl, table uint8[256][, rect]) over the same
+    slice: the CopyPaste / ClassMix / CutMix composite, taken per pixel before resampling (and before the flip): where
+    table[src_lbl] != 0 and, with a rect (frame coordinates), inside it"""
     if paste is not None:
-        p_img, p_lbl, table = paste
+        p_img, p_lbl, table = paste[:3]
         sel = np.asarray(table, np.uint8)[p_lbl] != 0
+        if paste_rect(paste) is not None:
+            y0, y1, x0, x1 = window_rect(paste_rect(paste), g.src)
+            box = np.zeros(sel.shape, bool)
+            box[y0:y1, x0:x1] = True
+            sel = sel & box
         raw_img = np.where(sel[..., None], p_img, raw_img)
         raw_lbl = np.where(sel, p_lbl, raw_lbl)
     if g.flip:
@@ -596,13 +619,14 @@ def execute_colour_host(ops, img, readers=None):
 def execute_plan_host(plan, img, lbl, paste=None, sliced=False):
     """numpy execution of a plan: -> ([image per view], [label per view]), always lists (augmentations.aug() returns a bare
     image / label for a single aug).  img / lbl: the source frame, or with `sliced` the slices plan_window(plan) of it
-    (what a worker hands over); paste = (source image, source label, table) of CopyPaste.run_plan, sliced likewise."""
+    (what a worker hands over); paste = (source image, source label, table[, rect]) of a preprocessor's run_plan, its
+    arrays sliced likewise (the rect stays in frame coordinates)."""
     g = plan[0]["ops"][0][1]
     if not sliced:
         y1, y2, x1, x2 = g.src
         img, lbl = img[y1:y2, x1:x2], lbl[y1:y2, x1:x2]
         if paste is not None:
-            paste = (paste[0][y1:y2, x1:x2], paste[1][y1:y2, x1:x2], paste[2])
+            paste = (paste[0][y1:y2, x1:x2], paste[1][y1:y2, x1:x2]) + tuple(paste[2:])
     cur, label = execute_geometry_host(g, img, lbl, paste)
     imgs, lbls = [], []
     for k, v in enumerate(plan):
@@ -621,6 +645,18 @@ REC_WORDS = 20
 # per (view, sample): kind, offset of the finished view, n ops, then (type, blob offset of the table) x MAX_OPS
 OPS_WORDS = 4 + 2 * MAX_OPS
 KIND_PLAN, KIND_FINISHED, KIND_STORE = 0, 1, 2
+# kind 0 / kind 2 whose paste is confined to a rectangle (CutMix): the paste table's 256 bytes are followed by ry0, ry1, rx0,
+# rx1 as little-endian int32 in WINDOW coordinates, clipped (an empty rectangle has ry0 == ry1)
+KIND_PLAN_RECT, KIND_STORE_RECT = 3, 4
+RECT_BYTES = 16
+
+
+def paste_table_bytes(table, rect_w=None):
+    """what R_PTAB points at: the 256 table bytes, + the window rectangle of a record of kind 3 / 4"""
+    table = np.ascontiguousarray(table, np.uint8).reshape(256)
+    if rect_w is None:
+        return table
+    return np.concatenate([table, np.asarray(rect_w, "<i4").reshape(4).view(np.uint8)])
 
 
 def _align(n, a=16):
@@ -654,6 +690,8 @@ def pack_sample(plan, raw_img, raw_lbl, paste=None):
         raw["paste_img"] = torch.from_numpy(np.ascontiguousarray(paste[0]))
         raw["paste_lbl"] = torch.from_numpy(np.ascontiguousarray(paste[1]))
         raw["paste_table"] = torch.from_numpy(np.ascontiguousarray(paste[2], np.uint8))
+        if paste_rect(paste) is not None:       # (frame coordinates; build_batch_tables translates it into the window's)
+            raw["paste_rect"] = torch.tensor(paste_rect(paste), dtype=torch.int64)
     return {"raw": raw, "plan": plan}
 
 
@@ -668,8 +706,8 @@ def _add_fda_views(raw, plan):
 def pack_store_sample(plan, index, row, paste=None):
     """what a worker returns for a planned sample whose frame is resident in the device store: no frame bytes.  index /
     row: the frame's dataset index and its row of the residency table (image offset, label offset, H, W);
-    paste = (source index, its row, uint8[256] table) of CopyPaste.run_plan_index with a resident source of the frame's
-    shape.  The FDA target views are decoded and resized here, in the worker, as in pack_sample."""
+    paste = (source index, its row, uint8[256] table[, rect]) of a preprocessor's run_plan_index with a resident source of
+    the frame's shape.  The FDA target views are decoded and resized here, in the worker, as in pack_sample."""
     rows = torch.full((2, 4), -1, dtype=torch.int64)
     rows[0] = torch.as_tensor(row, dtype=torch.int64)
     raw = {"store": (int(index), -1), "store_rows": rows}
@@ -677,6 +715,8 @@ def pack_store_sample(plan, index, row, paste=None):
         raw["store"] = (int(index), int(paste[0]))
         rows[1] = torch.as_tensor(paste[1], dtype=torch.int64)
         raw["paste_table"] = torch.from_numpy(np.ascontiguousarray(paste[2], np.uint8))
+        if paste_rect(paste) is not None:
+            raw["paste_rect"] = torch.tensor(paste_rect(paste), dtype=torch.int64)
     _add_fda_views(raw, plan)
     return {"raw": raw, "plan": plan}
 
@@ -707,6 +747,7 @@ def build_batch_tables(samples):
                              % (shp, v, out, n_views))
     ops = np.zeros((n_views, B, OPS_WORDS), np.int64)
     store_idx = np.full((B, 2), -1, np.int64)
+    store_rect = np.full((B, 4), -1, np.int64)
     max_ch = 1
     for b, s in enumerate(samples):
         raw, r = s["raw"], recs[b]
@@ -719,6 +760,7 @@ def build_batch_tables(samples):
             continue
         g = s["plan"][0]["ops"][0][1]
         ch, cw = g.src[1] - g.src[0], g.src[3] - g.src[2]
+        rect_w = window_rect(raw["paste_rect"].tolist(), g.src) if "paste_rect" in raw else None
         if "store" in raw:                   # the windows stay where they are: offsets of their first pixels in the store
             (io, lo, fh, fw), (pio, plo, ph, pw) = raw["store_rows"].tolist()
             first = g.src[0] * fw + g.src[2]
@@ -729,7 +771,10 @@ def build_batch_tables(samples):
             if raw["store"][1] >= 0:
                 if pio < 0 or plo < 0 or (ph, pw) != (fh, fw):
                     raise ValueError("device_aug: paste source of %dx%d at %d for a frame of %dx%d" % (ph, pw, pio, fh, fw))
-                r[R_PIMG], r[R_PLBL], r[R_PTAB] = pio + first * 3, plo + first, blob.add(raw["paste_table"].numpy())
+                r[R_PIMG], r[R_PLBL] = pio + first * 3, plo + first
+                r[R_PTAB] = blob.add(paste_table_bytes(raw["paste_table"].numpy(), rect_w))
+                if rect_w is not None:
+                    r[R_KIND], store_rect[b] = KIND_STORE_RECT, raw["paste_rect"].tolist()
             store_idx[b] = raw["store"]
         else:
             if tuple(raw["img"].shape) != (ch, cw, 3) or tuple(raw["lbl"].shape) != (ch, cw):
@@ -739,7 +784,9 @@ def build_batch_tables(samples):
             r[R_IMG], r[R_LBL] = blob.add(raw["img"].numpy()), blob.add(raw["lbl"].numpy())
             if "paste_img" in raw:
                 r[R_PIMG], r[R_PLBL] = blob.add(raw["paste_img"].numpy()), blob.add(raw["paste_lbl"].numpy())
-                r[R_PTAB] = blob.add(raw["paste_table"].numpy())
+                r[R_PTAB] = blob.add(paste_table_bytes(raw["paste_table"].numpy(), rect_w))
+                if rect_w is not None:
+                    r[R_KIND] = KIND_PLAN_RECT
         r[R_HLO], r[R_HN], r[R_HK], r[R_HT] = tabs.add(g.hlo), tabs.add(g.hn), tabs.add(g.hk), g.hk.shape[1]
         r[R_VLO], r[R_VN], r[R_VK], r[R_VT] = tabs.add(g.vlo), tabs.add(g.vn), tabs.add(g.vk), g.vk.shape[1]
         r[R_NX], r[R_NY] = tabs.add(g.nx), tabs.add(g.ny)
@@ -777,6 +824,8 @@ def build_batch_tables(samples):
          "meta": torch.tensor([n_views, out[0], out[1], max_ch, int(multi)], dtype=torch.int64)}
     if (store_idx[:, 0] >= 0).any():         # (frame index, paste source index | -1) of the KIND_STORE samples, -1 elsewhere
         t["store_idx"] = torch.from_numpy(store_idx)
+        if (store_rect[:, 0] >= 0).any():    # the FRAME rectangle of the KIND_STORE_RECT samples (their copy_paste_mask), -1 elsewhere
+            t["store_rect"] = torch.from_numpy(store_rect)
     return t
 
 
@@ -803,25 +852,28 @@ def is_device_aug_batch(batch):
 
 def _store_copy_paste_mask(t, store, device):
     """the batch's copy_paste_mask [B, H, W] uint8 ON THE DEVICE, the bytes the worker path delivers: a worker's mask where
-    it made one, else where(table[lbl_src], lbl_src, 255) from the resident source label (255 everywhere without a source)"""
+    it made one, else where(table[lbl_src] and inside the paste's rectangle, lbl_src, 255) from the resident source label
+    (255 everywhere without a source): ONE launch of hiast_aug_paste_mask_u8 for all the frames without a worker's mask"""
+    from hiast_amd import kernels as K
     masks, idx = t["cp_masks"], t["store_idx"].tolist()
     shapes = {tuple(m.shape) if m is not None else tuple(int(v) for v in store.frames[idx[b][0], 2:])
               for b, m in enumerate(masks)}
     if len(shapes) != 1:
         raise ValueError("device_aug: copy_paste_mask of frames of different sizes in one batch: %s" % sorted(shapes))
-    out = torch.empty((len(masks),) + shapes.pop(), dtype=torch.uint8, device=device)
-    blob = None
+    H, W = shapes.pop()
+    out = torch.empty((len(masks), H, W), dtype=torch.uint8, device=device)
+    rects = t["store_rect"].tolist() if "store_rect" in t else None
+    rows = []                                   # (source label offset | -1, table offset, y0, y1, x0, x1, frame of `out`, 0)
     for b, m in enumerate(masks):
         if m is not None:
             out[b].copy_(m, non_blocking=True)
         elif idx[b][1] < 0:
-            out[b].fill_(255)
+            rows.append((-1, 0, 0, 0, 0, 0, b, 0))
         else:
-            if blob is None:
-                blob = t["blob"].to(device, non_blocking=True)
-            ptab = int(t["recs"][b, R_PTAB])
-            src = store.label(idx[b][1])
-            out[b] = torch.where(blob[ptab:ptab + 256][src.long()] != 0, src, torch.full_like(src, 255))
+            rect = rects[b] if rects is not None and rects[b][0] >= 0 else (0, H, 0, W)
+            rows.append((int(store.frames[idx[b][1], 1]), int(t["recs"][b, R_PTAB])) + tuple(rect) + (b, 0))
+    if rows:
+        K.paste_mask_u8(store.buffer, t["blob"].to(device, non_blocking=True), np.array(rows, np.int64), out)
     return out
 
 

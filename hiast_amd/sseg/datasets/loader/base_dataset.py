@@ -92,7 +92,7 @@ class BaseDataset(Dataset):
             if paste:
                 src, cp_mask = self.preprocessor.run_plan(img, lbl)
                 if src is not None:
-                    src = (src[0][y1:y2, x1:x2], src[1][y1:y2, x1:x2], src[2])
+                    src = (src[0][y1:y2, x1:x2], src[1][y1:y2, x1:x2]) + tuple(src[2:])
             out = device_aug.pack_sample(plan, img[y1:y2, x1:x2], lbl[y1:y2, x1:x2], src)
         out["image_paths"] = path
         if cp_mask is not None:
@@ -116,11 +116,13 @@ class BaseDataset(Dataset):
         plan = device_aug.plan_sample(self.aug_fun, (row[2], row[3]), level=int(getattr(self, "device_aug_level", 1)))
         ok, src = not device_aug.needs_host(plan), None
         if ok and paste:
-            p_index, p_table = self.preprocessor.run_plan_index()
+            pre = self.preprocessor       # (CutMix sizes its rectangle by the frame's shape: the residency row has it)
+            drawn = pre.run_plan_index((row[2], row[3])) if getattr(pre, "plan_takes_shape", False) else pre.run_plan_index()
+            p_index, p_table = drawn[:2]
             if p_index is not None:
                 p_row = table[p_index].tolist()
                 ok = self.preprocessor.dataset_copy_from is self and p_row[0] >= 0 and p_row[2:] == row[2:]
-                src = (p_index, p_row, p_table)
+                src = (p_index, p_row, p_table) + tuple(drawn[2:])
         if not ok:
             random.setstate(state)
             if paste:

@@ -10,7 +10,16 @@ reference's, so a seeded run reproduces its outputs (tests/golden/copy_paste.npz
 
 Deviation (documented in DESIGN.md): for SYNTHIA the reference sets the three absent classes'
 value to inf, which turns the sampling probabilities into NaN and makes np.random.choice raise
-(preprocessor.py:18-19,31-40); here those classes get probability 0 instead."""
+(preprocessor.py:18-19,31-40); here those classes get probability 0 instead.
+
+PREPROCESSOR['ClassMix'] and PREPROCESSOR['CutMix'] — the two other values the reference documents for
+cfg.preprocessor.type and does not build (additions).  Both share CopyPaste's surface (run, run_plan,
+run_plan_index) and are pure plans: a source index, a class table and, for CutMix, a rectangle, all drawn from
+np.random in a documented order that reads no pixel, so the same draws serve the worker path, the bytes path and the
+path over device-resident frames.  A paste tuple of theirs may carry a 4th element, rect = (y0, y1, x0, x1) in frame
+coordinates, half-open; absent or None = the whole frame (what CopyPaste returns)."""
+import math
+
 import numpy as np
 from PIL import Image
 
@@ -141,3 +150,118 @@ class CopyPaste:
             dst[...] = keep
             np.copyto(lbl[r0:r1, c0:c1], lbl_[r0:r1, c0:c1], where=sub)
         return img, lbl, mask
+
+
+class _MixBase:
+    """what ClassMix and CutMix share: the source frame comes from dataset_copy_from, the composite is CopyPaste's
+    per-pixel select (table[lbl_src] != 0, inside the rectangle: image and label take the source's bytes) and
+    copy_paste_mask = the source label where pasted, 255 elsewhere.  draw(shape) is the whole of a sample's randomness."""
+    plan_takes_shape = True            # run_plan_index(shape): the destination frame's (H, W), known without a decode
+
+    def __init__(self, cfg, dataset_copy_from, init_class_value=None):
+        self.cfg = cfg
+        self.dataset_copy_from = dataset_copy_from
+
+    def draw(self, shape):
+        """-> (source index | None, uint8[256] table | None, rect | None)"""
+        raise NotImplementedError
+
+    def _source(self, j, img, lbl):
+        img_, lbl_, _ = self.dataset_copy_from.load_data(j)
+        if img.shape != img_.shape:
+            img_, lbl_ = CopyPaste.resize(img_, lbl_, lbl.shape)
+        return img_, lbl_
+
+    @staticmethod
+    def _select(table, lbl_, rect):
+        sel = np.asarray(table, np.uint8)[lbl_] != 0
+        if rect is not None:
+            y0, y1, x0, x1 = rect
+            box = np.zeros(sel.shape, bool)
+            box[y0:y1, x0:x1] = True
+            sel &= box
+        return sel
+
+    def run(self, img, lbl):
+        """-> (img, lbl, copy_paste_mask); img and lbl are composited in place, as CopyPaste.run does"""
+        mask = np.full(lbl.shape, 255, dtype=np.uint8)
+        j, table, rect = self.draw(lbl.shape)
+        if j is None:
+            return img, lbl, mask
+        img_, lbl_ = self._source(j, img, lbl)
+        sel = self._select(table, lbl_, rect)
+        np.copyto(mask, lbl_, where=sel)
+        np.copyto(img, img_, where=sel[..., None])
+        np.copyto(lbl, lbl_, where=sel)
+        return img, lbl, mask
+
+    def run_plan(self, img, lbl):
+        """-> ((source image, source label, table[, rect]) | None, copy_paste_mask): run()'s draws, nothing composited"""
+        mask = np.full(lbl.shape, 255, dtype=np.uint8)
+        j, table, rect = self.draw(lbl.shape)
+        if j is None:
+            return None, mask
+        img_, lbl_ = self._source(j, img, lbl)
+        np.copyto(mask, lbl_, where=self._select(table, lbl_, rect))
+        return ((img_, lbl_, table) if rect is None else (img_, lbl_, table, rect)), mask
+
+    def run_plan_index(self, shape=None):
+        """-> (source index | None, table | None[, rect]): run()'s draws, nothing decoded"""
+        j, table, rect = self.draw(shape)
+        return (j, table) if rect is None else (j, table, rect)
+
+
+@PREPROCESSOR.register("ClassMix")
+class ClassMix(_MixBase):
+    """half of the source frame's classes, as in DACS.  Draws: j = randint(len(dataset_copy_from)); classes(j) = the sorted
+    class ids whose samples_with_class list holds frame j's file name (the inversion of get_samples_with_class(), built
+    once here: no decode, the same on every path — NOT np.unique of the label, and it inherits the "lowest 10 % per class
+    dropped" rule of stat_samples_with_class); none: no paste and no further draw; else
+    chosen = choice(classes(j), size=(n + 1) // 2, replace=False)."""
+
+    def __init__(self, cfg, dataset_copy_from, init_class_value=None):
+        super().__init__(cfg, dataset_copy_from, init_class_value)
+        self.classes_of = [[] for _ in range(len(dataset_copy_from))]
+        for c, names in sorted(dataset_copy_from.get_samples_with_class().items()):
+            for name in names:
+                self.classes_of[dataset_copy_from.get_file_to_idx(name)].append(int(c))
+        self.classes_of = [sorted(set(cs)) for cs in self.classes_of]
+
+    def draw(self, shape=None):
+        j = int(np.random.randint(len(self.dataset_copy_from)))
+        classes = self.classes_of[j]
+        if not classes:
+            return None, None, None
+        chosen = np.random.choice(classes, size=(len(classes) + 1) // 2, replace=False)
+        table = np.zeros(256, dtype=np.uint8)
+        table[np.asarray(chosen, dtype=np.int64)] = 1
+        return j, table, None
+
+
+@PREPROCESSOR.register("CutMix")
+class CutMix(_MixBase):
+    """one rectangle of the source frame, label included (a source 255 stays 255).  Draws, with (H, W) the destination
+    frame's shape and (lo, hi) = cfg.preprocessor.cut_mix.area_range: j = randint(len(dataset_copy_from));
+    p = uniform(lo, hi); fh = exp(uniform(log(p), 0)), fw = p / fh (both in [p, 1]);
+    bh = min(H, max(1, int(fh * H + 0.5))), bw likewise; y0 = randint(0, H - bh + 1); x0 = randint(0, W - bw + 1)."""
+
+    def __init__(self, cfg, dataset_copy_from, init_class_value=None):
+        super().__init__(cfg, dataset_copy_from, init_class_value)
+        lo, hi = (float(v) for v in cfg.preprocessor.cut_mix.area_range)
+        if not 0.0 < lo <= hi <= 1.0:
+            raise ValueError("preprocessor.cut_mix.area_range %r: 0 < lo <= hi <= 1 is required" % ([lo, hi],))
+        self.area_range = (lo, hi)
+
+    def draw(self, shape=None):
+        if shape is None:
+            raise ValueError("CutMix: the destination frame's (H, W) is required")
+        H, W = int(shape[0]), int(shape[1])
+        j = int(np.random.randint(len(self.dataset_copy_from)))
+        p = np.random.uniform(*self.area_range)
+        fh = math.exp(np.random.uniform(math.log(p), 0.0))
+        fw = p / fh
+        bh = min(H, max(1, int(fh * H + 0.5)))
+        bw = min(W, max(1, int(fw * W + 0.5)))
+        y0 = int(np.random.randint(0, H - bh + 1))
+        x0 = int(np.random.randint(0, W - bw + 1))
+        return j, np.ones(256, dtype=np.uint8), (y0, y0 + bh, x0, x0 + bw)

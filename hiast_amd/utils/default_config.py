@@ -187,6 +187,7 @@ mut_training:
 preprocessor:
   type: null
   copy_paste: {mode: original, name: normal, selected_num_classes: 14, gamma: 0.99}
+  cut_mix: {area_range: [0.25, 0.5]}
 """)
 
 

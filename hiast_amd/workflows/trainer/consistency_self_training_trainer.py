@@ -10,9 +10,9 @@ import torch
 
 from hiast_amd import functional as HF
 from hiast_amd.sseg.datasets import utils as du
-from hiast_amd.sseg.datasets.preprocessor import CopyPaste
 from hiast_amd.utils import utils
-from hiast_amd.utils.registry.registries import DATASET, TRAINER
+from hiast_amd.sseg.datasets import preprocessor  # noqa: F401  (fills PREPROCESSOR)
+from hiast_amd.utils.registry.registries import DATASET, PREPROCESSOR, TRAINER
 from hiast_amd.utils.result_recorder import ResultRecorder
 from hiast_amd.workflows.trainer.base_trainer import BaseTrainer
 
@@ -125,14 +125,18 @@ class ConsistencySelfTrainingTrainer(BaseTrainer):
         assert cfg.cst_training.is_enabled, "consistency training should be enabled"
         assert len(cfg.dataset.target.aug_type) in (1, 2), \
             "target domain dataset should have 1 or 2 augmentations for consistency training"
-        assert cfg.preprocessor.type == "CopyPaste"
+        assert cfg.preprocessor.type in PREPROCESSOR, \
+            "preprocessor.type %r (registered: %s)" % (cfg.preprocessor.type, sorted(PREPROCESSOR))
 
     def build_train_data_reader(self):
         t = self.cfg.dataset.target
-        self.class_value = np.load(os.path.join(t.pseudo_dir, "..", "class_mean_probabilities.npy"))
+        cmp_path = os.path.join(t.pseudo_dir, "..", "class_mean_probabilities.npy")
+        # (the generator's per-class confidence: CopyPaste picks its hard classes from it, the mixing preprocessors do not)
+        required = self.cfg.preprocessor.type == "CopyPaste"
+        self.class_value = np.load(cmp_path) if required or os.path.exists(cmp_path) else None
         self.t_dataset = DATASET[t.type](self.cfg, t.json_path, t.image_dir, pseudo_dir=t.pseudo_dir,
                                          aug_type=t.aug_type, num_classes=self.cfg.dataset.num_classes)
-        self.preprocessor = CopyPaste(self.cfg, self.t_dataset, self.class_value)
+        self.preprocessor = PREPROCESSOR[self.cfg.preprocessor.type](self.cfg, self.t_dataset, self.class_value)
         self.t_dataset.set_preprocessor(self.preprocessor)
         self.t_sampler, self.t_loader = self._loader(self.t_dataset, self.cfg.train.batch_size, True, True)
         self.t_iter = iter(self.t_loader)

@@ -573,6 +573,42 @@ int hiast_aug_geometry_store_u8(const int64_t* recs, const uint8_t* blob, const 
 int hiast_normalize_gather_u8(const uint8_t* store, const int64_t* offsets, float* out, int B, int64_t HW, const float* mean,
                               const float* std, hiast_stream_t stream);
 
+/* ---- K15 for the mixing preprocessors (cfg.preprocessor.type: ClassMix | CutMix; hiast_amd/sseg/datasets/preprocessor.py) ---
+ * Two more record kinds, a paste confined to a rectangle: HIAST_MIX_KIND_PLAN_RECT (3) = kind 0 and
+ * HIAST_MIX_KIND_STORE_RECT (4) = kind 2 (HIAST_STORE_KIND), whose paste_table word points at HIAST_MIX_TABLE_BYTES
+ * bytes of the blob: the 256 table bytes, then ry0, ry1, rx0, rx1 as little-endian int32 — the rectangle in the
+ * coordinates of the record's (unflipped) window, half-open, clipped to [0, ch] x [0, cw]; empty: ry0 == ry1.  The offset
+ * is a multiple of 4.  Kinds 0, 1 and 2 keep their bytes and their meaning.
+ * hiast_aug_geometry_mix_u8: hiast_aug_geometry_store_u8 for every kind 0..4 — the same two launches, the same
+ *   arithmetic; the select on load is table[paste_lbl] && ry0 <= row < ry1 && rx0 <= col < rx1 in the horizontal pass and
+ *   in the label gather (kinds 0 and 2: the table alone).  A row outside the rectangle reads no byte of the paste source,
+ *   a column outside it neither.  `store` may be NULL when no record is of kind 2 or 4 (such a record is then left
+ *   unwritten).  `blob` must be 4-byte aligned.
+ *   hiast_aug_geometry_u8 / hiast_aug_geometry_store_u8 know kinds 0..2 only.  Records live on the device, so no launch
+ *   entry can read a kind: the refusal is hiast_aug_records_check on the HOST copy, which the wrappers
+ *   (hiast_amd/kernels.py) call before every geometry entry with that entry's max_kind.
+ * hiast_aug_records_check: HOST recs [B][HIAST_AUG_REC_WORDS] and HOST blob of blob_bytes -> 0, or HIAST_E_ARG for a kind
+ *   outside 0..max_kind (max_kind: 1, 2 or 4), and for a record of kind 3 / 4 without paste offsets, whose table +
+ *   rectangle is not inside the blob at a multiple of 4, or whose rectangle leaves [0, ch] x [0, cw] or has y0 > y1 or
+ *   x0 > x1.  Launches nothing.
+ * hiast_aug_paste_mask_u8: the copy_paste_mask of n frames of H x W in ONE launch.  prm: DEVICE int64 [n][8] = (offset
+ *   of the source frame's label in the store | -1, blob offset of its 256-byte table, y0, y1, x0, x1 in FRAME
+ *   coordinates, index of the frame of `out` to write, 0): out[frame][y][x] = (table[src] && y0 <= y < y1 && x0 <= x < x1)
+ *   ? src : 255; a source of -1 gives 255 everywhere and reads nothing.  16 bytes per lane where the source label and
+ *   the output frame are 16-byte aligned (frames of the store are), single bytes over the tail.  Offsets and frame
+ *   indices are bounds-checked by the host wrapper; the rectangle is clamped to the frame.
+ * The launch entries refuse a null pointer and a non-positive extent (HIAST_E_ARG) and the extents their neighbours refuse
+ * (HIAST_E_RANGE) before any launch. */
+#define HIAST_MIX_KIND_PLAN_RECT 3
+#define HIAST_MIX_KIND_STORE_RECT 4
+#define HIAST_MIX_TABLE_BYTES (256 + 16)
+int hiast_aug_records_check(const int64_t* recs, const uint8_t* blob, int64_t blob_bytes, int B, int max_kind);
+int hiast_aug_geometry_mix_u8(const int64_t* recs, const uint8_t* blob, const uint8_t* store, const int32_t* tabs,
+                              uint8_t* tmp, uint8_t* img_out, uint8_t* lbl_out, int B, int max_ch, int oh, int ow,
+                              hiast_stream_t stream);
+int hiast_aug_paste_mask_u8(const int64_t* prm, const uint8_t* store, const uint8_t* blob, uint8_t* out, int n, int H, int W,
+                            hiast_stream_t stream);
+
 /* ---- K15b: the colour ops of the device-side sample path, every level -------------------------------------------
  * Level 1: LUT, OpenCV's fixed-point gray, cv2.equalizeHist (per-channel histogram -> float64 table, rint).  Level 2
  * (cfg.dataset.device_aug_level: 2): ColorJitter and GaussianBlur as plan ops.  All byte-identical to
