@@ -328,7 +328,7 @@ __device__ __forceinline__ float4 bna_apply4(const float4 v, const float (&sc)[4
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float t = fmaf(o[k], sc[k], sh[k]);
-        o[k] = RELU ? (t > 0.f ? t : 0.f) : t;
+        o[k] = RELU ? ((t > 0.f || t != t) ? t : 0.f) : t;      // a NaN stays (the rule of hiast_hip.h)
     }
     return make_float4(o[0], o[1], o[2], o[3]);
 }
@@ -344,7 +344,7 @@ __device__ __forceinline__ uint4 bna_apply8(const uint4 v, const float (&sc)[8],
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const float t = fmaf(o[k], sc[2 * q + k], sh[2 * q + k]);
-            o[k] = RELU ? (t > 0.f ? t : 0.f) : t;
+            o[k] = RELU ? ((t > 0.f || t != t) ? t : 0.f) : t;      // a NaN stays (the rule of hiast_hip.h)
         }
         pk[q] = (unsigned)__bfloat16_as_ushort(__float2bfloat16(o[0])) |
                 ((unsigned)__bfloat16_as_ushort(__float2bfloat16(o[1])) << 16);

@@ -457,6 +457,9 @@ extern "C" int hiast_pack_conv_weight(const float* w, int N, int K, int taps, in
     const int planes = fmt;                              // 1 bf16 rows | 2 split-bf16 planes | 3 fp16 rows
     if (!hiast_fmt_ok(fmt) || transpose < 0 || transpose > 2) return HIAST_E_RANGE;
     if (transpose == 2 && !wpt) return HIAST_E_ARG;
+    // split planes: a 32-channel slab of the reduction axis holds hi | lo (64 elements), so a ragged last slab would put its lo
+    // half into the next row (behind wp for the last one): every form written needs whole slabs
+    if (planes == HIAST_FMT_SPLIT_BF16 && ((transpose != 1 && K % 32 != 0) || (transpose != 0 && N % 32 != 0))) return HIAST_E_RANGE;
     const long long total = (long long)N * K * taps;
     if (N % 64 == 0 && K % 64 == 0 && taps <= 9 && !((((uintptr_t)wp) | ((uintptr_t)wpt)) & 15)) {
         const dim3 tg((unsigned)((N / 64) * (K / 64)));
@@ -492,7 +495,8 @@ namespace hiast {
 // K9f: BN(eval) + ReLU + MaxPool2d(3, stride 2, padding 1) of the library stem's output, written in the operand format of
 // the trunk kernels — one pass instead of three (BN + ReLU, torch's pooling kernel, split / cast).  Thread = 8 channels of an
 // output pixel (its nine inputs: the 8 lanes of a pixel read one contiguous run); scale / shift are derived once per thread
-// (the channel group of a thread is fixed along its grid-stride walk: the stride is a multiple of C / 8).
+// (the channel group of a thread is fixed along its grid-stride walk: the stride is a multiple of C / 8 whenever a thread
+// strides at all, i.e. when the grid is capped).  A NaN activation passes the ReLU and takes the maximum, as in hiast_stem_eval.
 // INK: 0 fp32 input, 1 bf16, 2 fp16; F16 (PL = 1): fp16 output rows
 template <int INK, int PL, bool F16 = false>
 __global__ __launch_bounds__(256) void stem_tail_kernel(const void* __restrict__ xv, const float* __restrict__ gamma,
@@ -549,9 +553,9 @@ __global__ __launch_bounds__(256) void stem_tail_kernel(const void* __restrict__
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     float t = fmaf(v[k], sc[k], sh[k]);
-                    t = t > 0.f ? t : 0.f;
+                    t = (t > 0.f || t != t) ? t : 0.f;                             // a NaN stays (the rule of hiast_hip.h)
                     if (INK != 0) t = H16<INK == 2>::dec(H16<INK == 2>::enc(t));   // the 16-bit activation the pooling kernel saw
-                    m[k] = t > m[k] ? t : m[k];
+                    m[k] = (t > m[k] || t != t) ? t : m[k];                        // ... and takes the maximum
                 }
             }
         }
@@ -593,7 +597,8 @@ extern "C" int hiast_stem_tail(const void* x, int dtype, const float* gamma, con
     if ((long long)B * H * W * C >= (1ll << 40)) return HIAST_E_RANGE;
     long long nb = (total + 255) / 256;
     int grid = (int)(nb > 16384 ? 16384 : nb);
-    {   // grid-stride = multiple of G, so that a thread keeps its channel group
+    if (grid < nb) {   // a thread strides: grid-stride = multiple of G, so that it keeps its channel group.  (A launch of nb
+        // blocks is one pass: nothing to keep, any nb will do.)
         long long a = 256, g = G;
         while (a) { const long long t = g % a; g = a; a = t; }
         const int need = (int)(G / g);

@@ -23,7 +23,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 st_bf16x8;
 typedef __attribute__((ext_vector_type(4))) float st_f32x4;
 
 constexpr int ST_PH = 4, ST_PW = 6;                   // pooled tile (9 x 13 = 117 conv outputs: 8 pixel tiles, one per wave)
-constexpr int ST_CR = 2 * ST_PH + 1, ST_CC = 2 * ST_PW + 1;   // 9 x 17 convolution outputs
+constexpr int ST_CR = 2 * ST_PH + 1, ST_CC = 2 * ST_PW + 1;   // 9 x 13 convolution outputs
 constexpr int ST_NPX = ST_CR * ST_CC;                 // 117
 constexpr int ST_PT = (ST_NPX + 15) / 16;             // 8 pixel tiles of 16
 constexpr int ST_IR = 2 * ST_CR + 5;                  // 23 input rows
@@ -181,11 +181,21 @@ __global__ __launch_bounds__(512) void stem_eval_kernel(const float* __restrict_
             }
             // activation fragments of kernel row ky + 1 are requested before the MFMAs of row ky (two register sets)
             st_bf16x8 xh[2][2], xl[2][2];
+            // the eighth input pixel of a row (kx = 7: the upper half of the kg = 3 fragment) meets a zero weight, but it is a real
+            // pixel one column right of the 7-wide window: a NaN or inf there must not reach this output (0 x NaN = NaN).
+            // (Two v_and per fragment: 2 % of the kernel in the 16-bit formats, 5 % with split planes, measured at B = 8,
+            // 1024 x 512; masking at use instead of at the request costs the same.)
+            const unsigned k7 = kg == 3 ? 0u : 0xFFFFFFFFu;
+            auto drop7 = [&](const unsigned char* p) {
+                uint4 v = *reinterpret_cast<const uint4*>(p);
+                v.z &= k7; v.w &= k7;
+                return __builtin_bit_cast(st_bf16x8, v);
+            };
             auto fetch = [&](int set, int ky) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    xh[set][j] = *reinterpret_cast<const st_bf16x8*>(xrow[j] + ky * ST_IC * 8);
-                    if (PL == 2) xl[set][j] = *reinterpret_cast<const st_bf16x8*>(xrow[j] + IN_BYTES + ky * ST_IC * 8);
+                    xh[set][j] = drop7(xrow[j] + ky * ST_IC * 8);
+                    if (PL == 2) xl[set][j] = drop7(xrow[j] + IN_BYTES + ky * ST_IC * 8);
                 }
             };
             fetch(0, 0);

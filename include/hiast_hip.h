@@ -390,14 +390,30 @@ int hiast_xconv_dgrad_gated_bn_stats_rows(int64_t M, int K, int N);
 int hiast_xconv_dgrad_gated_bn_stats(const void* dy, const void* wpt, const void* res, const void* res_gate, const void* bn_x,
                                      const void* bn_mask, const float* save_mean, const float* save_invstd, void* dx,
                                      float* partial, int64_t M, int K, int N, int fmt, hiast_stream_t stream);
+/* hiast_pack_conv_weight: w fp32 [N][K][taps] (torch layout) -> wp [N][taps][planes*K] in operand format fmt (transpose = 0),
+ * the adjoint [K][taps flipped][planes*N] (transpose = 1), or both (transpose = 2: forward in wp, adjoint in wpt; wpt is not
+ * looked at otherwise).  Element (row, tap, reduction channel k) sits at ((row*taps + tap)*planes*KO) + k for one plane and at
+ * + (k / 32)*64 + k % 32 for split planes, its lo half 32 elements further (KO = reduction channels of that form).  Any N, K,
+ * taps > 0 and any alignment are taken; N % 64 == 0, K % 64 == 0, taps <= 9 and 16-byte aligned wp / wpt take the tiled kernel
+ * (the same bits).  Split planes need whole 32-channel slabs of the reduction axis of every form written — K % 32 == 0 for
+ * transpose 0 and 2, N % 32 == 0 for transpose 1 and 2 — else HIAST_E_RANGE before any launch (a ragged slab's lo half would
+ * land in the next row, and behind wp for the last one). */
 int hiast_pack_conv_weight(const float* w, int N, int K, int taps, int fmt, int transpose, void* wp, void* wpt,
                            hiast_stream_t stream);
 int hiast_split_planes(float* x, void* planes, int64_t M, int C, int inverse, hiast_stream_t stream);
+/* NaN rule of hiast_stem_eval, hiast_stem_tail, hiast_bn_act_nhwc_infer (relu = 1) and hiast_maxpool3x3s2_nhwc_fwd: a NaN
+ * activation passes the ReLU (NaN < 0 is false) and takes a pooling window's maximum, as in ATen's relu and max_pool2d; every
+ * other value keeps the bits it had (-0.0 behind a ReLU is +0.0). */
 /* K9f hiast_stem_tail: bn1 (eval) -> ReLU -> MaxPool2d(3, stride 2, padding 1) of the stem convolution's output
  * (ResNet.forward, sseg/models/modules/resnet.py:180-184: x = conv1(x); bn1; relu; maxpool) in ONE pass, written in the
- * operand format of the trunk kernels.  x: channels-last [B,H,W,C] fp32 (dtype 0) or bf16 (dtype 1; the ReLU output is
- * rounded to bf16 before the maximum, as a bf16 module path does); out: planes = 2: split planes [B,Ho,Wo,2*C] (C % 32 == 0),
- * planes = 1: bf16 [B,Ho,Wo,C]; Ho = (H-1)/2+1, Wo = (W-1)/2+1; C % 8 == 0; gamma / beta may be NULL (1 / 0). */
+ * operand format of the trunk kernels.  x: channels-last [B,H,W,C] fp32 (dtype 0), bf16 (dtype 1) or fp16 (dtype 2); for the
+ * 16-bit inputs the ReLU output is rounded to the input's type before the maximum, as a half-precision module path does.
+ * out in format fmt: HIAST_FMT_SPLIT_BF16: split planes [B,Ho,Wo,2*C] (C % 32 == 0), HIAST_FMT_BF16 / HIAST_FMT_FP16: 16-bit
+ * rows [B,Ho,Wo,C]; every dtype goes with every fmt.  Ho = (H-1)/2+1, Wo = (W-1)/2+1; C % 8 == 0; x and out 16-byte aligned;
+ * B*H*W*C < 2^40; gamma / beta may be NULL (1 / 0).
+ * Grid: ceil(B*Ho*Wo*(C/8) / 256) blocks in one pass whatever C is; above 16384 blocks the grid is capped and rounded down to
+ * a multiple of need = (C/8) / gcd(256, C/8), so that a striding thread keeps its channel group.  HIAST_E_RANGE only for a C
+ * whose need exceeds the cap (C/8 > 16384 with no factor of 2 to spare: no workload has one). */
 int hiast_stem_tail(const void* x, int dtype /* 0 fp32 | 1 bf16 | 2 fp16 */, const float* gamma, const float* beta,
                     const float* mean, const float* var, float eps, void* out, int fmt /* HIAST_FMT_* of out */, int B, int H,
                     int W, int C, hiast_stream_t stream);
