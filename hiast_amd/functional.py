@@ -4,6 +4,7 @@ CUDA(HIP) tensors only.  Autocast: the losses and the pseudo-label kernels take 
 even under apex O1); the ASPP head and the trunk convolutions / BatchNorms run in bf16 on channels-last activations
 under bf16 autocast (_Aspp2Fn, _ConvNhwcFn, _BnActNhwcFn) and in fp32 otherwise (_AsppFn, _BnActFn).
 """
+import contextlib
 import os
 
 import torch
@@ -258,14 +259,6 @@ def _sync_world(bn):
     return 1
 
 
-_BN3_FUSION = os.environ.get("HIAST_NO_BN3_FUSION", "0") != "1"     # bn3's backward sums from the next block's conv1 data gradient
-_OWN_S2_DGRAD = os.environ.get("HIAST_LIB_DGRAD_S2", "0") != "1"      # (=1: the library's data gradient for the strided 3x3)
-
-# read ONCE at import: the ranks of a job must issue the collectives of the statistics group at matching points, a switch
-# that is looked up per call could differ between them (or change between a forward and its backward)
-_NO_ASYNC_STAT = os.environ.get("HIAST_NO_ASYNC_STAT", "0") == "1"
-
-
 def _stat_all_reduce(t, async_op=False):
     """SyncBN exchange: sum of the per-rank statistics, on the communicator reserved for it (utils/comm.py: these
     [C,2] reduces sit between two kernels of the main stream and must not queue behind DDP's 32 MB gradient buckets or
@@ -326,13 +319,133 @@ def _is_cl(t):
     return t.dim() == 4 and t.permute(0, 2, 3, 1).is_contiguous()
 
 
+class IdentityLink:
+    """Identity-branch hand-off between the autograd nodes of ONE identity bottleneck (DESIGN: trunk hand-offs): conv1's
+    data-gradient epilogue adds the ReLU-masked gradient of the identity branch, so bn3's backward neither writes that masked
+    copy nor returns it for autograd to add.
+    armed: set by conv1's forward (_ConvNhwcFn) when its backward will do so; read by bn3's forward (_BnActNhwcFn).
+    gated: (dy, bit mask or y), left by bn3's backward, taken ONCE by conv1's backward (which runs after it)."""
+    __slots__ = ("armed", "gated")
+
+    def __init__(self):
+        self.armed, self.gated = False, None
+
+    def take(self):
+        gated, self.gated = self.gated, None
+        return gated
+
+
+class BnBwdLink:
+    """Backward sums (Σg, Σ g*xhat) of ONE BatchNorm from the data-gradient epilogue of the ONE convolution that consumes its
+    output: no statistics pass of the BatchNorm's own.
+    gate / saved / world: written by the BatchNorm's forward (register) — gate 2 (ReLU, no residual: bn1, bn2) with saved =
+    (x, mean, invstd, gamma, beta); gate 3 (residual + ReLU, bit mask: bn3) with saved = (x, mask, mean, invstd); gate 0 =
+    nobody registered.  Read by the consuming convolution's forward (arm or not) and backward (the kernel's operands).
+    partial / sums: written by that convolution's backward (deliver), taken ONCE by the BatchNorm's backward, which runs after
+    it (take); dropped by the BatchNorm's next forward when that backward was pruned (discard)."""
+    __slots__ = ("gate", "saved", "world", "partial", "sums")
+
+    def __init__(self):
+        self.gate, self.saved, self.world, self.partial, self.sums = 0, None, 1, None, None
+
+    def register(self, gate, saved, world):
+        self.gate, self.saved, self.world = gate, saved, world
+
+    def deliver(self, partial):
+        """per-block sums from the epilogue.  SyncBN: reduce them now and start their all-reduce; the weight gradient that
+        follows (50 - 300 us, on the main stream under DDP) runs while the [C,2] exchange (a latency, ~30 us on 8 devices) is
+        in flight — the BatchNorm's backward then finds the reduced sums instead of waiting for the exchange"""
+        if self.world != 1 and not SW.on("HIAST_NO_ASYNC_STAT"):
+            sums = K.bn_nhwc_stats_from_partial(partial)
+            self.sums = (sums, _stat_all_reduce(sums, async_op=True))
+        else:
+            self.partial = partial
+
+    def take(self):
+        """-> the delivered sums, reduced over blocks and ranks, or None (nothing delivered: the caller runs its own pass)"""
+        early, partial, self.sums, self.partial = self.sums, self.partial, None, None
+        if early is not None:
+            _stat_wait(early[1])
+            return early[0]
+        if partial is None:
+            return None
+        sums = K.bn_nhwc_stats_from_partial(partial)
+        if self.world != 1:
+            _stat_all_reduce(sums)
+        return sums
+
+    def discard(self):
+        """leftovers of an iteration whose backward through the BatchNorm was pruned (its input needed no gradient) while the
+        consuming convolution's backward had already started the exchange: finish it, drop the sums"""
+        early, self.sums, self.partial = self.sums, None, None
+        if early is not None:
+            _stat_wait(early[1])
+
+
+class SharedInputLink:
+    """Two convolutions read the SAME x (conv1 and the stride-1 downsample of a stage-entry block): the one whose backward runs
+    first (the giver: conv1, created later in the forward) hands its data gradient over instead of returning it, the other (the
+    taker) adds it in the epilogue of its own data-gradient launch: x receives ONE gradient and autograd's add kernel over the
+    block input (33 - 134 MB, three per step) is not launched.  Which of the two a convolution is: Links.gives.
+    taker: set by the taker's forward (join).  The giver's forward, which runs after it, takes part only then — if the
+    downsample leg took another path (e.g. its BatchNorm in eval mode while bn1 trains) nothing would ever take the gradient
+    and conv1's input gradient would be dropped silently.
+    dx: parked by the giver's backward (give), taken ONCE by the taker's backward (take), which also sets taken: in a second
+    backward over a retained graph the giver returns its gradient itself."""
+    __slots__ = ("taker", "dx", "taken")
+
+    def __init__(self):
+        self.taker, self.dx, self.taken = False, None, False
+
+    def join(self, gives):
+        """forward -> whether this convolution takes part"""
+        if not gives:
+            self.taker = True
+        return self.taker
+
+    def give(self, dx):
+        """-> what the giver still has to return itself"""
+        if dx is None or self.taken:
+            return dx
+        self.dx = dx
+        return None
+
+    def take(self):
+        dx, self.dx, self.taken = self.dx, None, True
+        return dx
+
+
+class Links:
+    """The hand-offs ONE trunk node takes part in, as the one argument conv_nhwc / bn_act pass on (any may be None).
+    idt: IdentityLink — a convolution arms and takes it, a BatchNorm fills it;  bn: BnBwdLink — for a convolution the
+    BatchNorm whose output it reads, for a BatchNorm its own;  shared / gives: SharedInputLink and this convolution's role;
+    wgrad: (jobs, slot, weight view) of wgroup_weights."""
+    __slots__ = ("idt", "bn", "shared", "gives", "wgrad")
+
+    def __init__(self, idt=None, bn=None, shared=None, gives=False, wgrad=None):
+        self.idt, self.bn, self.shared, self.gives, self.wgrad = idt, bn, shared, gives, wgrad
+
+
+NO_LINKS = Links()
+
+
+def set_bn3_link(y, link):
+    """bn3's link travels on the block output y, where the next block's conv1 finds it (bn3_link) — and nobody else: it
+    vanishes when anything other than the next block consumes y.  Correct only while that block is the sole consumer of y."""
+    if link.gate == 3:
+        y._hiast_bn3 = link
+
+
+def bn3_link(x):
+    return getattr(x, "_hiast_bn3", None)
+
+
 class _BnActNhwcFn(torch.autograd.Function):
     """_BnActFn on channels-last bf16 activations (hiast_bn_nhwc_*): the layout of the hand-written convolution
     kernels, so the student forward / backward needs no NCHW<->NHWC transposes."""
 
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, running_mean, running_var, momentum, eps, relu, world, partial, box,
-                stat_box=None):
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, momentum, eps, relu, world, partial, links):
         # batch statistics: from the producing convolution's epilogue when it delivered them, else one pass over x
         count = float(x.shape[0] * x.shape[2] * x.shape[3])
         # ReLU gate of the backward: recomputed from x when there is no residual input; with a residual the forward
@@ -354,30 +467,16 @@ class _BnActNhwcFn(torch.autograd.Function):
         y, sm, si = out[:3]
         ctx.save_for_backward(x, out[3] if want_mask else (y if ctx.gate == 1 else None), gamma, beta, sm, si)
         ctx.has_res, ctx.world, ctx.count = res is not None, world, count
-        # identity-branch hand-off (see Bottleneck.forward): when the block's first convolution has announced that its
-        # data-gradient epilogue will add the ReLU-masked gradient of the identity branch itself, this backward
-        # neither writes that masked copy (dres) nor returns it for autograd to add
-        ctx.box = box if (box is not None and box.get("armed") and ctx.gate in (1, 3)) else None
-        # statistics hand-off (see _ConvNhwcFn): the data-gradient launch of the ONE convolution that consumes y can emit
-        # this layer's backward sums (Σg, Σ g*xhat) from its epilogue; it needs x and the batch statistics for that
-        ctx.stat_box = None
-        if stat_box is not None:
-            # leftovers of a previous iteration whose backward through THIS layer was pruned (its input needed no gradient)
-            # while the consuming convolution's backward had already started the exchange: finish it, drop the sums
-            left = stat_box.pop("bwd_sums", None)
-            if left is not None:
-                _stat_wait(left[1])
-            stat_box.pop("bwd_partial", None)
-        if stat_box is not None and ctx.gate == 2:
-            stat_box["bn"] = (x.detach(), sm, si, gamma, beta)
-            stat_box["world"] = world
-            ctx.stat_box = stat_box
-        elif stat_box is not None and ctx.gate == 3:
-            # bn3 of a bottleneck (residual + ReLU, gate bits written): conv1 of the NEXT identity block may deliver this layer's
-            # backward sums from the epilogue that writes the gradient of y (hiast_xconv_dgrad_gated_bn_stats, round 4)
-            stat_box["bn3"] = (x.detach(), out[3], sm, si)
-            stat_box["world"] = world
-            ctx.stat_box = stat_box
+        # IdentityLink: armed by the block's conv1 -> this backward leaves (dy, gate) there instead of writing dres
+        ctx.idt = links.idt if (links.idt is not None and links.idt.armed and ctx.gate in (1, 3)) else None
+        # BnBwdLink: the convolution that consumes y needs x and the batch statistics to emit this layer's backward sums
+        ctx.link = None
+        if links.bn is not None:
+            links.bn.discard()
+            if ctx.gate in (2, 3):
+                links.bn.register(ctx.gate, (x.detach(), sm, si, gamma, beta) if ctx.gate == 2 else (x.detach(), out[3], sm, si),
+                                  world)
+                ctx.link = links.bn
         return y
 
     @staticmethod
@@ -386,26 +485,18 @@ class _BnActNhwcFn(torch.autograd.Function):
         if dy.dtype != x.dtype:
             dy = dy.to(x.dtype)
         dy = dy.contiguous(memory_format=torch.channels_last)
-        fused = ctx.stat_box.pop("bwd_partial", None) if ctx.stat_box is not None else None
-        early = ctx.stat_box.pop("bwd_sums", None) if ctx.stat_box is not None else None
-        if early is not None:          # SyncBN: the consuming convolution's backward has reduced its epilogue sums and started
-            sums, work = early         # the all-reduce BEFORE its weight gradient: the exchange ran beside that kernel
-            _stat_wait(work)
-        else:
-            if fused is not None:      # per-block sums from the epilogue of the consuming convolution's data gradient
-                sums = K.bn_nhwc_stats_from_partial(fused)
-            else:
-                sums = K.bn_nhwc_bwd_stats(dy, y, x, gamma, beta, sm, si, ctx.gate)
+        sums = ctx.link.take() if ctx.link is not None else None
+        if sums is None:
+            sums = K.bn_nhwc_bwd_stats(dy, y, x, gamma, beta, sm, si, ctx.gate)
             if ctx.world != 1:
                 _stat_all_reduce(sums)
         want_p = gamma is not None and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
-        handoff = ctx.box is not None and ctx.needs_input_grad[1]
+        handoff = ctx.idt is not None and ctx.needs_input_grad[1]
         dx, dres, dg, db = K.bn_nhwc_bwd_apply(dy, y, x, gamma, beta, sm, si, sums, ctx.count, ctx.gate,
                                                ctx.has_res and ctx.needs_input_grad[1] and not handoff, want_p)
         if handoff:
-            ctx.box["gated"] = (dy, y)            # (gradient, bit mask): consumed by the block's conv1 backward
-        return (dx, dres, dg if ctx.needs_input_grad[2] else None, db if ctx.needs_input_grad[3] else None,
-                None, None, None, None, None, None, None, None, None)
+            ctx.idt.gated = (dy, y)               # (gradient, bit mask): taken by the block's conv1 backward
+        return (dx, dres, dg if ctx.needs_input_grad[2] else None, db if ctx.needs_input_grad[3] else None) + (None,) * 8
 
 
 class _ConvNhwcFn(torch.autograd.Function):
@@ -417,41 +508,29 @@ class _ConvNhwcFn(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
-    def forward(ctx, x, weight, stride, dil, want_stats, box, packed, in_bn=None, wgroup=None, xsum=None, in_bn3=None):
+    def forward(ctx, x, weight, stride, dil, want_stats, packed, links):
         xv = x.permute(0, 2, 3, 1)
-        # in_bn3: x is the output of the PREVIOUS bottleneck (relu(bn3(.) + identity), registered there) and this is conv1 of an
-        # identity block whose backward adds the identity gradient itself: its data gradient also delivers that bn3's sums
-        ctx.in_bn3 = None
-        if (in_bn3 is not None and "bn3" in in_bn3 and box is not None and stride == 1 and weight.shape[2] == 1
-                and ctx.needs_input_grad[0] and _BN3_FUSION
-                and K.xconv_dgrad_gated_bn_stats_ok(x.shape[0] * x.shape[2] * x.shape[3], weight.shape[0], weight.shape[1])):
-            ctx.in_bn3 = in_bn3
-        ctx.wgroup = wgroup                   # (group dict, slot): the weight gradient is deferred to _WGroupFn.backward
-        # xsum = (dict, role): two convolutions read the SAME x (conv1 and the stride-1 downsample of a stage-entry block).
-        # The one whose backward runs first ('give': conv1, created later in the forward) hands its data gradient over
-        # instead of returning it, the other ('take') adds it in the epilogue of its own data-gradient launch: x receives
-        # ONE gradient and autograd's add kernel over the block input (33 - 134 MB, three per step) is not launched.
-        ctx.xsum = xsum if (xsum is not None and stride == 1 and ctx.needs_input_grad[0]) else None
-        if ctx.xsum is not None:
-            # the 'take' convolution (the downsample: its forward runs first) announces itself; 'give' hands its gradient over only
-            # to a taker that exists — if the downsample leg took another path (e.g. its BatchNorm in eval mode while bn1 trains)
-            # nothing would ever pop the gradient and conv1's input gradient would be dropped silently
-            if ctx.xsum[1] == "take":
-                ctx.xsum[0]["taker"] = True
-            elif not ctx.xsum[0].get("taker"):
-                ctx.xsum = None
-        # in_bn: x = relu(bn(x0)) of a BatchNorm that registered itself there (and has no other consumer): the data
+        dgrad1 = stride == 1 and ctx.needs_input_grad[0]          # every hand-off rides on the stride-1 data-gradient launch
+        bn = links.bn if dgrad1 else None
+        # bn of gate 3: x is the output of the PREVIOUS bottleneck (relu(bn3(.) + identity), registered there) and this is conv1 of
+        # an identity block whose backward adds the identity gradient itself: its data gradient also delivers that bn3's sums
+        ctx.in_bn3 = bn if (bn is not None and bn.gate == 3 and links.idt is not None and weight.shape[2] == 1
+                            and not SW.on("HIAST_NO_BN3_FUSION") and K.xconv_dgrad_gated_bn_stats_ok(
+                                x.shape[0] * x.shape[2] * x.shape[3], weight.shape[0], weight.shape[1])) else None
+        # bn of gate 2: x = relu(bn(x0)) of a BatchNorm that registered itself there (and has no other consumer): the data
         # gradient of this convolution then also delivers that BatchNorm's backward sums (hiast_igemm_dgrad_bn_stats)
-        ctx.in_bn = in_bn if (in_bn is not None and "bn" in in_bn and stride == 1 and ctx.needs_input_grad[0]
-                              and not SW.on("HIAST_NO_BN_BWD_FUSION")) else None
+        ctx.in_bn = bn if (bn is not None and bn.gate == 2 and not SW.on("HIAST_NO_BN_BWD_FUSION")) else None
+        ctx.wgroup = None if links.wgrad is None else links.wgrad[:2]     # (jobs, slot): dW is deferred to _WGroupFn.backward
+        ctx.shared = links.shared if (links.shared is not None and dgrad1 and links.shared.join(links.gives)) else None
+        ctx.gives = links.gives
         ctx.set_materialize_grads(False)     # no zero tensor for the (non-differentiable) statistics output
         ctx.wpt = None
-        ctx.box = None
-        if box is not None and stride == 1 and ctx.needs_input_grad[0]:
-            box["armed"] = True                    # this conv's backward will take over the identity-branch gradient
-            ctx.box = box
+        ctx.idt = links.idt if dgrad1 else None
+        if ctx.idt is not None:
+            ctx.idt.armed = True                   # this conv's backward will take over the identity-branch gradient
         # (the adjoint weight serves the stride-1 data gradients and the transposed form of the 3x3 / stride-2 one)
-        need_adj = ctx.needs_input_grad[0] and (stride == 1 or (stride == 2 and weight.shape[2] == 3 and dil == 1 and _OWN_S2_DGRAD))
+        own_s2 = not SW.on("HIAST_LIB_DGRAD_S2")
+        need_adj = ctx.needs_input_grad[0] and (stride == 1 or (stride == 2 and weight.shape[2] == 3 and dil == 1 and own_s2))
         if packed is not None and packed[0] is not None and (not need_adj or packed[1] is not None):
             wp, ctx.wpt = packed                   # kernel-format copies kept current by ResNet.prepack (one launch)
         elif need_adj:                             # forward + adjoint (data-gradient) weight in one pack launch
@@ -469,8 +548,12 @@ class _ConvNhwcFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dy, _dpartial=None):
-        if dy is None:
-            return None, None, None, None, None, None, None, None, None, None, None
+        dx, dw = _ConvNhwcFn.grads(ctx, dy) if dy is not None else (None, None)
+        return dx, dw, None, None, None, None, None
+
+    @staticmethod
+    def grads(ctx, dy):
+        """-> (dx, dw) of backward"""
         x, weight = ctx.saved_tensors
         stride, dil = ctx.geo
         if dy.dtype != x.dtype:
@@ -480,52 +563,38 @@ class _ConvNhwcFn(torch.autograd.Function):
         pad = dil if k == 3 else 0
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dx = dw = None
-        own_s2 = need_x and stride == 2 and k == 3 and dil == 1 and _OWN_S2_DGRAD
+        own_s2 = need_x and stride == 2 and k == 3 and dil == 1 and not SW.on("HIAST_LIB_DGRAD_S2")
         lib_x = need_x and stride != 1 and not own_s2
         if own_s2:              # hiast_igemm_dgrad_s2: the transposed form of the tile kernel (was the library's, round 3)
             wpt = ctx.wpt if ctx.wpt is not None else K.pack_conv_weight(weight, K.fmt_of(x), transpose=True)
             dx = K.igemm_dgrad_s2(dy.permute(0, 2, 3, 1), wpt, x.shape[2], x.shape[3]).permute(0, 3, 1, 2)
         if need_x and stride == 1:
             wpt = ctx.wpt if ctx.wpt is not None else K.pack_conv_weight(weight, K.fmt_of(x), transpose=True)
-            gated = ctx.box.pop("gated", None) if ctx.box is not None else None
+            gated = ctx.idt.take() if ctx.idt is not None else None
             if ctx.in_bn is not None and gated is None:
-                bx, sm, si, gamma, beta = ctx.in_bn["bn"]
+                bx, sm, si, gamma, beta = ctx.in_bn.saved
                 dxv, bpartial = K.igemm_dgrad_bn_stats(dy.permute(0, 2, 3, 1), wpt, dil, bx.permute(0, 2, 3, 1), gamma, beta,
                                                        sm, si)
-                if ctx.in_bn.get("world", 1) != 1 and not _NO_ASYNC_STAT:
-                    # SyncBN: reduce the per-block sums now and start their all-reduce; the weight gradient below (50 - 300 us,
-                    # on the main stream under DDP) runs while the [C,2] exchange (a latency, ~30 us on 8 devices) is in
-                    # flight — the BatchNorm's backward then finds the reduced sums instead of waiting for the exchange
-                    bsums = K.bn_nhwc_stats_from_partial(bpartial)
-                    ctx.in_bn["bwd_sums"] = (bsums, _stat_all_reduce(bsums, async_op=True))
-                else:
-                    ctx.in_bn["bwd_partial"] = bpartial
+                ctx.in_bn.deliver(bpartial)
                 dx = dxv.permute(0, 3, 1, 2)
             elif gated is not None and ctx.in_bn3 is not None and gated[1].dtype == torch.uint8:
                 # ... and the backward sums of the previous block's bn3, whose output's gradient this launch writes (K9e')
-                bx3, bmask, sm3, si3 = ctx.in_bn3["bn3"]
+                bx3, bmask, sm3, si3 = ctx.in_bn3.saved
                 dxv, bpartial = K.xconv_dgrad_gated_bn_stats(dy.permute(0, 2, 3, 1), wpt, gated[0].permute(0, 2, 3, 1), gated[1],
                                                              bx3.permute(0, 2, 3, 1), bmask, sm3, si3)
-                if ctx.in_bn3.get("world", 1) != 1 and not _NO_ASYNC_STAT:
-                    bsums = K.bn_nhwc_stats_from_partial(bpartial)
-                    ctx.in_bn3["bwd_sums"] = (bsums, _stat_all_reduce(bsums, async_op=True))
-                else:
-                    ctx.in_bn3["bwd_partial"] = bpartial
+                ctx.in_bn3.deliver(bpartial)
                 dx = dxv.permute(0, 3, 1, 2)
             elif gated is not None:    # + dy_block * (y_block > 0): the identity branch's gradient, in the epilogue
                 dx = K.igemm_bn_act(dy.permute(0, 2, 3, 1), wpt, 1, None, gated[0].permute(0, 2, 3, 1), False, 1, dil,
                                     res_gate=(gated[1] if gated[1].dtype == torch.uint8
                                               else gated[1].permute(0, 2, 3, 1))).permute(0, 3, 1, 2)
             else:
-                other = None
-                if ctx.xsum is not None and ctx.xsum[1] == "take":
-                    other = ctx.xsum[0].pop("dx", None)       # the gradient conv1's backward left for us (same shape as dx)
-                    ctx.xsum[0]["taken"] = True
+                # the taker of a SharedInputLink: + the gradient conv1's backward left for us (same shape as dx)
+                other = ctx.shared.take() if (ctx.shared is not None and not ctx.gives) else None
                 dx = K.igemm_bn_act(dy.permute(0, 2, 3, 1), wpt, 1, None, None if other is None else other.permute(0, 2, 3, 1),
                                     False, 1, dil).permute(0, 3, 1, 2)
-        if ctx.xsum is not None and ctx.xsum[1] == "give" and dx is not None and not ctx.xsum[0].get("taken"):
-            ctx.xsum[0]["dx"] = dx             # the downsample convolution's backward (it runs after this one) adds it
-            dx = None
+        if ctx.shared is not None and ctx.gives:
+            dx = ctx.shared.give(dx)           # the downsample convolution's backward (it runs after this one) adds it
         own_w = need_w and not SW.on("HIAST_LIB_WGRAD") and K.conv_wgrad_preferred(
             weight.shape[1], weight.shape[0], k, stride) and (k == 1 or dy.shape[3] >= 4)
         small_w = need_w and not own_w and not SW.on("HIAST_LIB_WGRAD") and K.conv_wgrad_small_supported(
@@ -538,16 +607,11 @@ class _ConvNhwcFn(torch.autograd.Function):
             # grouped weight gradient (hiast_conv_wgrad_group_nhwc): hand the operands to the bottleneck's _WGroupFn node,
             # whose backward runs when the last of the block's convolutions has delivered its pair, and return a
             # zero-stride placeholder of the weight's shape (no memory, no kernel) for autograd to pass on to it
-            grp, slot = ctx.wgroup
-            grp["jobs"][slot] = (dy.permute(0, 2, 3, 1), x.permute(0, 2, 3, 1), k, stride, dil)
-            return dx, _wgrad_token(weight), None, None, None, None, None, None, None, None, None
-        side = wgrad_side_stream(x.device) if (need_w and not lib_x) else None
-        main = torch.cuda.current_stream()
-        if side is not None:
-            side.wait_stream(main)
-            dy.record_stream(side)
-            x.record_stream(side)
-        with torch.cuda.stream(side if side is not None else main):
+            jobs, slot = ctx.wgroup
+            jobs[slot] = (dy.permute(0, 2, 3, 1), x.permute(0, 2, 3, 1), k, stride, dil)
+            return dx, _wgrad_token(weight)
+        # (not on the side stream when the library computes the data gradient in the same call)
+        with wgrad_stream(x.device, (dy, x), need_w and not lib_x) as made:
             if own_w:            # transposed-read GEMM over the pixel index (hiast_conv_wgrad_nhwc)
                 dw = K.conv_wgrad_nhwc(dy.permute(0, 2, 3, 1), x.permute(0, 2, 3, 1), k, stride, dil)
                 need_w = False
@@ -568,9 +632,8 @@ class _ConvNhwcFn(torch.autograd.Function):
                     if dw.stride() != weight.stride() and dw.is_contiguous() and weight.is_contiguous():
                         dw = dw.view(-1).view(weight.shape)     # 1x1 kernels: canonical strides for the size-1 dims
                                                                 # (DDP compares strides with its bucket view literally)
-        if side is not None and dw is not None:
-            dw.record_stream(main)
-        return dx, dw, None, None, None, None, None, None, None, None, None
+            made.append(dw)
+        return dx, dw
 
 
 _wgrad_tokens = {}
@@ -595,33 +658,22 @@ class _WGroupFn(torch.autograd.Function):
     hooks) complete, from this node."""
 
     @staticmethod
-    def forward(ctx, grp, *ws):
-        ctx.grp = grp
+    def forward(ctx, jobs, *ws):
+        ctx.jobs = jobs     # one slot per weight: (dY, X, k, stride, dil), written by its convolution's backward, emptied by ours
         ctx.set_materialize_grads(False)
         return tuple(w.view_as(w) for w in ws)
 
     @staticmethod
     def backward(ctx, *tokens):
-        grp = ctx.grp
-        jobs = grp["jobs"]
+        jobs = ctx.jobs
         live = [i for i, j in enumerate(jobs) if j is not None and tokens[i] is not None]
         # a convolution that did not take the grouped path after all (a shape its backward sends elsewhere) has returned
         # its real weight gradient: passed through
         out = [tokens[i] if jobs[i] is None else None for i in range(len(jobs))]
         if live:
-            dev = jobs[live[0]][1].device
-            side = wgrad_side_stream(dev)
-            main = torch.cuda.current_stream()
-            if side is not None:
-                side.wait_stream(main)
-                for i in live:
-                    jobs[i][0].record_stream(side)
-                    jobs[i][1].record_stream(side)
-            with torch.cuda.stream(side if side is not None else main):
-                dws = K.conv_wgrad_group([jobs[i] for i in live]) if len(live) > 1 else [K.conv_wgrad_nhwc(*jobs[live[0]])]
-            for i, dw in zip(live, dws):
-                if side is not None:
-                    dw.record_stream(main)
+            with wgrad_stream(jobs[live[0]][1].device, [t for i in live for t in jobs[i][:2]]) as made:
+                made.extend(K.conv_wgrad_group([jobs[i] for i in live]) if len(live) > 1 else [K.conv_wgrad_nhwc(*jobs[live[0]])])
+            for i, dw in zip(live, made):
                 out[i] = dw
         for i in range(len(jobs)):
             jobs[i] = None                                  # drop the operand references
@@ -629,16 +681,18 @@ class _WGroupFn(torch.autograd.Function):
 
 
 def wgroup_weights(convs, x):
-    """-> (group dict, [weight views]) when the weight gradients of `convs` (the convolutions of one bottleneck) can be
-    computed by one grouped launch on the training path of x, else (None, None)"""
+    """-> per convolution of `convs` (the convolutions of one bottleneck) what conv_nhwc takes as Links.wgrad: (jobs, slot,
+    weight view) for the members of ONE grouped weight-gradient launch on the training path of x, None for the others (all of
+    them when no group pays)"""
+    out = [None] * len(convs)
     if (len(convs) < 2 or len(convs) > 4 or SW.on("HIAST_NO_WGROUP")
             or SW.on("HIAST_LIB_WGRAD") or not torch.is_grad_enabled()):
-        return None, None
+        return out
     for c in convs:
         k = c.kernel_size[0]
         if (not c.weight.requires_grad or not conv_nhwc_ok(x, c) or c.stride[0] != 1
                 or not K.conv_wgrad_preferred(c.in_channels, c.out_channels, k, 1)):
-            return None, None
+            return out
     # A grouped launch is ONE round of (tiles x pixel ranges) <= 256 blocks: worth it when that fills the chip.  layer3:
     # 4 + 9 + 4 tiles x 15 ranges = 255 blocks (190 us against 239 us one by one); layer4: 16 + 36 + 16 tiles x 3 ranges
     # = 204 blocks leave a fifth of the CUs idle (698 against 622 us) — there only the 1x1 pair is grouped (32 tiles x 8
@@ -654,15 +708,12 @@ def wgroup_weights(convs, x):
     if fill(member) < 0.9:
         member = [i for i in member if convs[i].kernel_size[0] == 1]
         if len(member) < 2 or fill(member) < 0.9:
-            return None, None
-    grp = {"jobs": [None] * len(member)}
-    views = _WGroupFn.apply(grp, *[convs[i].weight for i in member])
-    wv = [None] * len(convs)
-    slot = [None] * len(convs)
-    for s_, i in enumerate(member):
-        wv[i], slot[i] = views[s_], s_
-    grp["slot"] = slot
-    return grp, wv
+            return out
+    jobs = [None] * len(member)
+    views = _WGroupFn.apply(jobs, *[convs[i].weight for i in member])
+    for slot, i in enumerate(member):
+        out[i] = (jobs, slot, views[slot])
+    return out
 
 
 class _StemConvFn(torch.autograd.Function):
@@ -690,17 +741,9 @@ class _StemConvFn(torch.autograd.Function):
         dyv = dy.permute(0, 2, 3, 1)
         if not dyv.is_contiguous():
             dyv = dyv.contiguous()
-        side = wgrad_side_stream(x.device)
-        main = torch.cuda.current_stream()
-        if side is not None:
-            side.wait_stream(main)
-            dyv.record_stream(side)
-            x.record_stream(side)
-        with torch.cuda.stream(side if side is not None else main):
-            dw = K.stem_wgrad(x, dyv)
-        if side is not None:
-            dw.record_stream(main)
-        return None, dw, None
+        with wgrad_stream(x.device, (dyv, x)) as made:
+            made.append(K.stem_wgrad(x, dyv))
+        return None, made[0], None
 
 
 def stem_conv_train(x, conv):
@@ -901,6 +944,26 @@ def wgrad_side_stream(device):
     return st
 
 
+@contextlib.contextmanager
+def wgrad_stream(device, inputs, on=True):
+    """run the body on the weight-gradient side stream of `device` (on the current stream when there is none, or `on` is false):
+    the side stream waits for the current one and `inputs` are recorded on it; the gradients the body appends to the list
+    it is given are recorded back on the current stream"""
+    side = wgrad_side_stream(device) if on else None
+    main = torch.cuda.current_stream()
+    if side is not None:
+        side.wait_stream(main)
+        for t in inputs:
+            t.record_stream(side)
+    made = []
+    with torch.cuda.stream(side if side is not None else main):
+        yield made
+    if side is not None:
+        for t in made:
+            if t is not None:
+                t.record_stream(main)
+
+
 def wgrad_stream_join():
     """make the current stream wait for every weight gradient issued on a side stream (call before optimizer.step()
     or before reading .grad)"""
@@ -968,11 +1031,10 @@ class _SubsampleClFn(torch.autograd.Function):
         return g, None
 
 
-def conv_nhwc(x, conv, want_stats=False, box=None, in_bn=None, wgroup=None, xsum=None, in_bn3=None):
-    """-> y, or (y, partial) with want_stats (see igemm_bn_act); box: identity-branch hand-off of a bottleneck;
-    in_bn: statistics hand-off of the BatchNorm whose output x is (bn_act(..., stat_box=in_bn))"""
+def conv_nhwc(x, conv, want_stats=False, links=NO_LINKS):
+    """-> y, or (y, partial) with want_stats (see igemm_bn_act); links: the hand-offs this convolution's node takes part in"""
     w = conv.weight
-    wv = w if wgroup is None else wgroup[2]      # wgroup = (group dict, slot, this weight as it comes out of _WGroupFn)
+    wv = w if links.wgrad is None else links.wgrad[2]      # (this weight as it comes out of _WGroupFn)
     fmt = K.fmt_of(x)
     fwd = conv.__dict__.get("_hiast_packed", {}).get(fmt)
     adj = conv.__dict__.get("_hiast_packed_adj", {}).get(fmt)
@@ -985,14 +1047,13 @@ def conv_nhwc(x, conv, want_stats=False, box=None, in_bn=None, wgroup=None, xsum
         # DDP copy the bucket view); autograd scatters the data gradient back into the skipped pixels
         x = _SubsampleClFn.apply(x, stride)
         stride = 1
-    return _ConvNhwcFn.apply(x, wv, stride, conv.dilation[0], bool(want_stats), box, packed, in_bn,
-                             None if wgroup is None else (wgroup[0], wgroup[1]), xsum, in_bn3)
+    return _ConvNhwcFn.apply(x, wv, stride, conv.dilation[0], bool(want_stats), packed, links)
 
 
 _nbt_batched = [False]      # set by ResNet.forward while it has already advanced every num_batches_tracked at once
 
 
-def bn_act(x, bn, res=None, relu=True, partial=None, box=None, stat_box=None):
+def bn_act(x, bn, res=None, relu=True, partial=None, links=NO_LINKS):
     """Fused replacement of `relu(bn(x) [+ res])` for a torch BatchNorm2d / SyncBatchNorm module `bn`
     (which keeps owning the parameters and running statistics)."""
     training = bn.training or (bn.running_mean is None)
@@ -1002,6 +1063,6 @@ def bn_act(x, bn, res=None, relu=True, partial=None, box=None, stat_box=None):
     if (training and x.dtype in H16 and _is_cl(x) and not x.is_contiguous()
             and K.bn_nhwc_supported(x.shape[1]) and (res is None or (res.dtype == x.dtype and _is_cl(res)))):
         return _BnActNhwcFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum, bn.eps, relu,
-                                  _sync_world(bn), partial, box, stat_box)
+                                  _sync_world(bn), partial, links)
     return _BnActFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum,
                           bn.eps, relu, _sync_world(bn) if training else 1)

@@ -35,14 +35,13 @@ def conv(m, x):
     return m(x)
 
 
-def conv_bn_act(cv, bn, x, res=None, relu=True, conv_box=None, bn_box=None, in_bn=None, stat_box=None, wgroup=None, xsum=None,
-                in_bn3=None):
+def conv_bn_act(cv, bn, x, res=None, relu=True, conv_links=HF.NO_LINKS, bn_links=HF.NO_LINKS):
     """relu?(bn(conv(x)) [+ res]).  On the channels-last bf16 training path the convolution's epilogue also
-    delivers the per-block sums the BatchNorm needs (one pass over the activation less); stat_box / in_bn: the same for
-    the BACKWARD sums — this BatchNorm registers itself in stat_box, the next conv_bn_act gets that dict as in_bn."""
+    delivers the per-block sums the BatchNorm needs (one pass over the activation less); conv_links / bn_links: the hand-offs
+    of the backward (HF.Links) the two autograd nodes take part in."""
     if x.is_cuda and x.dtype in HF.H16 and bn.training and HF.conv_nhwc_ok(x, cv):
-        y, partial = HF.conv_nhwc(x, cv, want_stats=True, box=conv_box, in_bn=in_bn, wgroup=wgroup, xsum=xsum, in_bn3=in_bn3)
-        return HF.bn_act(y, bn, res, relu, partial=partial, box=bn_box, stat_box=stat_box)
+        y, partial = HF.conv_nhwc(x, cv, want_stats=True, links=conv_links)
+        return HF.bn_act(y, bn, res, relu, partial=partial, links=bn_links)
     return bn_act(bn, conv(cv, x), res, relu)
 
 
@@ -86,34 +85,32 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def forward(self, x):
+        L = HF.Links
         # stage-entry block with a stride-1 downsample: conv1 and the downsample convolution read the same x; their two data
-        # gradients become one (HF._ConvNhwcFn xsum: conv1 hands its gradient to the downsample's data-gradient epilogue)
+        # gradients become one (HF.SharedInputLink: conv1 hands its gradient to the downsample's data-gradient epilogue)
         xs = None
         if (self.downsample is not None and self.downsample[0].stride == (1, 1) and x.is_cuda and x.dtype in HF.H16
                 and self.bn1.training and x.requires_grad and not HF.SW.on("HIAST_NO_XSUM")):
-            xs = {}
+            xs = HF.SharedInputLink()
         idt = x if self.downsample is None else conv_bn_act(self.downsample[0], self.downsample[1], x, relu=False,
-                                                            xsum=None if xs is None else (xs, "take"))
+                                                            conv_links=L(shared=xs))
         # identity blocks on the channels-last training path: conv1's data-gradient epilogue adds the ReLU-masked
-        # gradient of the identity branch itself (no masked copy written by bn3's backward, no separate add kernel);
-        # `box` is the hand-off between the two autograd nodes of this call
-        box = {} if (self.downsample is None and not HF.SW.on("HIAST_NO_IDT_HANDOFF")) else None
-        sb1, sb2 = {}, {}       # bn1 -> conv2's data gradient, bn2 -> conv3's: backward statistics from the dgrad epilogue
+        # gradient of the identity branch itself (no masked copy written by bn3's backward, no separate add kernel)
+        il = HF.IdentityLink() if (self.downsample is None and not HF.SW.on("HIAST_NO_IDT_HANDOFF")) else None
+        # bn1 -> conv2's data gradient, bn2 -> conv3's, bn3 -> conv1's of the NEXT block: backward sums from the dgrad epilogue
+        b1, b2, b3 = HF.BnBwdLink(), HF.BnBwdLink(), HF.BnBwdLink()
         # layer3 / layer4 on the 16-bit training path: the three weight gradients of the block are ONE grouped launch at the
         # end of its backward (HF._WGroupFn) instead of three launches that each fill the chip with partial tiles
-        grp, wv = (None, None)
+        wg = (None, None, None)
         if x.is_cuda and x.dtype in HF.H16 and self.bn1.training:
-            grp, wv = HF.wgroup_weights((self.conv1, self.conv2, self.conv3), x)
-        g = (lambda i: (grp, grp["slot"][i], wv[i]) if wv[i] is not None else None) if grp is not None else (lambda i: None)
-        # x may carry the registration of the previous block's bn3 (below): conv1's data gradient of an identity block then also
-        # delivers that BatchNorm's backward sums (HF._ConvNhwcFn in_bn3)
-        o = conv_bn_act(self.conv1, self.bn1, x, conv_box=box, stat_box=sb1, wgroup=g(0),
-                        xsum=None if xs is None else (xs, "give"), in_bn3=getattr(x, "_hiast_bn3", None) if box is not None else None)
-        o = conv_bn_act(self.conv2, self.bn2, o, in_bn=sb1, stat_box=sb2, wgroup=g(1))
-        sb3 = {}
-        y = conv_bn_act(self.conv3, self.bn3, o, res=idt, bn_box=box, in_bn=sb2, stat_box=sb3, wgroup=g(2))   # += identity, ReLU
-        if "bn3" in sb3:
-            y._hiast_bn3 = sb3         # read by the next block (the one consumer of y besides its identity path)
+            wg = HF.wgroup_weights((self.conv1, self.conv2, self.conv3), x)
+        # x may carry the link of the previous block's bn3 (below): conv1's data gradient of an identity block then also
+        # delivers that BatchNorm's backward sums
+        o = conv_bn_act(self.conv1, self.bn1, x, bn_links=L(bn=b1), conv_links=L(
+            idt=il, bn=HF.bn3_link(x) if il is not None else None, shared=xs, gives=True, wgrad=wg[0]))
+        o = conv_bn_act(self.conv2, self.bn2, o, conv_links=L(bn=b1, wgrad=wg[1]), bn_links=L(bn=b2))
+        y = conv_bn_act(self.conv3, self.bn3, o, res=idt, conv_links=L(bn=b2, wgrad=wg[2]), bn_links=L(idt=il, bn=b3))
+        HF.set_bn3_link(y, b3)         # read by the next block (the one consumer of y besides its identity path)
         return y
 
     def forward_eval_planes(self, x, fmt):

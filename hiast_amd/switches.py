@@ -6,7 +6,10 @@ the statistics communicator is a hang.  Tests flip them with `monkeypatch.setite
 import os
 
 _NAMES = ("HIAST_NO_BN_MASK", "HIAST_NO_BN_BWD_FUSION", "HIAST_LIB_WGRAD", "HIAST_NO_WGROUP", "HIAST_NO_XSUM",
-          "HIAST_NO_IDT_HANDOFF", "HIAST_LIB_STEM")
+          "HIAST_NO_IDT_HANDOFF", "HIAST_LIB_STEM",
+          "HIAST_NO_BN3_FUSION",      # bn3's backward sums from a pass of their own, not from the next block's conv1 data gradient
+          "HIAST_LIB_DGRAD_S2",       # the library's data gradient for the strided 3x3
+          "HIAST_NO_ASYNC_STAT")      # SyncBN backward: the exchange inside the BatchNorm's backward (changes the collective order)
 SWITCHES = {n: os.environ.get(n, "0") == "1" for n in _NAMES}
 # opt-IN paths (off unless set to "1"), kept apart from the opt-outs above; read once and flipped by tests the same way
 _OPT_IN_NAMES = ("HIAST_DISC_HIP", "HIAST_DISC_HIP_16BIT")

@@ -84,8 +84,8 @@ def test_layer4_block_groups_only_its_1x1_pair(monkeypatch):
     blk = Bottleneck(2048, 512, 1, 4).to(dev).train()
     x0 = torch.randn(1, 2048, 16, 24, device=dev).half().contiguous(memory_format=torch.channels_last)
     gy = torch.randn(1, 2048, 16, 24, device=dev).half().contiguous(memory_format=torch.channels_last)
-    grp, wv = HF.wgroup_weights((blk.conv1, blk.conv2, blk.conv3), x0)
-    assert grp is not None and wv[1] is None and grp["slot"] == [0, None, 1]
+    wg = HF.wgroup_weights((blk.conv1, blk.conv2, blk.conv3), x0)         # per convolution: (jobs, slot, weight view) or None
+    assert wg[1] is None and wg[0][0] is wg[2][0] and [wg[0][1], wg[2][1]] == [0, 1]
     res = {}
     for mode in ("single", "group"):
         monkeypatch.setitem(SW.SWITCHES, "HIAST_NO_WGROUP", mode == "single")
@@ -195,7 +195,7 @@ def test_igemm_dgrad_s2_vs_fp32_on_the_rounded_operands(dt, cfg):
 
 def test_strided_bottleneck_backward_without_the_library(monkeypatch):
     """a layer2.0-shaped block (3x3 stride 2 + strided downsample) on the 16-bit training path: own transposed data gradient
-    against the library's (HIAST_LIB_DGRAD_S2=1 is read at import: the flag is patched on the module)"""
+    against the library's (HIAST_LIB_DGRAD_S2=1)"""
     from hiast_amd import functional as HF
     from hiast_amd.sseg.models.modules.resnet import Bottleneck
     import torch.nn as nn
@@ -207,7 +207,7 @@ def test_strided_bottleneck_backward_without_the_library(monkeypatch):
     gy = torch.randn(2, 512, 16, 24, device=dev).half().contiguous(memory_format=torch.channels_last)
     res = {}
     for own in (False, True):
-        monkeypatch.setattr(HF, "_OWN_S2_DGRAD", own)
+        monkeypatch.setitem(SW.SWITCHES, "HIAST_LIB_DGRAD_S2", not own)
         blk.zero_grad()
         src = x0.clone().requires_grad_(True)
         with torch.autocast("cuda", dtype=torch.float16):
@@ -327,7 +327,7 @@ def test_small_channel_weight_gradients_on_two_streams_do_not_share_partials(mon
         return [getattr(blk, n).weight.grad.clone() for n in names] + [blk.downsample[0].weight.grad.clone()]
     try:
         for own_s2 in (True, False):        # (False: the round-3 arrangement — library data gradient, weight gradient on main)
-            monkeypatch.setattr(HF, "_OWN_S2_DGRAD", own_s2)
+            monkeypatch.setitem(SW.SWITCHES, "HIAST_LIB_DGRAD_S2", not own_s2)
             want = run(False)
             for _ in range(4):
                 got = run(True)
@@ -376,7 +376,7 @@ def test_xconv_dgrad_gated_bn_stats_vs_the_two_separate_launches(dt, shape):
 def test_two_identity_bottlenecks_bn3_sums_from_the_next_blocks_conv1(monkeypatch):
     """two layer3-shaped identity blocks in a row on the 16-bit training path: the first block's bn3 takes its backward sums from
     the epilogue of the second block's conv1 data gradient (no statistics pass of its own) — against the unfused form
-    (HF._BN3_FUSION = False): same outputs, gradients up to the order of the fp32 sums; the fused path really ran"""
+    (HIAST_NO_BN3_FUSION=1): same outputs, gradients up to the order of the fp32 sums; the fused path really ran"""
     import torch.nn as nn
     from hiast_amd import functional as HF
     from hiast_amd import kernels as K
@@ -400,7 +400,7 @@ def test_two_identity_bottlenecks_bn3_sums_from_the_next_blocks_conv1(monkeypatc
     monkeypatch.setattr(K, "bn_nhwc_bwd_stats", spy_s)
     res = {}
     for fuse in (False, True):
-        monkeypatch.setattr(HF, "_BN3_FUSION", fuse)
+        monkeypatch.setitem(SW.SWITCHES, "HIAST_NO_BN3_FUSION", not fuse)
         calls["fused"] = calls["stats3"] = 0
         net.zero_grad()
         src = x0.clone().requires_grad_(True)

@@ -26,9 +26,9 @@ def _r16(a, dt):
 
 # ------------------------------------------------------------------------------------------------ round-4 advisor findings
 def test_shared_input_gradient_is_not_dropped_without_a_taker():
-    """the xsum hand-off of a stage-entry block (conv1 'gives' its data gradient to the downsample convolution's epilogue): a
-    'give' convolution whose partner never registered as taker (its leg took another path) must return its input gradient itself
-    — round 4 parked it in the shared dict, where nothing picked it up"""
+    """the shared-input hand-off of a stage-entry block (conv1 gives its data gradient to the downsample convolution's epilogue): a
+    giving convolution whose partner never registered as taker (its leg took another path) must return its input gradient itself
+    — round 4 parked it in the shared link, where nothing picked it up"""
     import torch.nn as nn
     from hiast_amd import functional as HF
     torch.manual_seed(7)
@@ -37,23 +37,23 @@ def test_shared_input_gradient_is_not_dropped_without_a_taker():
     x0 = torch.randn(2, 512, 24, 40, device=dev).half().contiguous(memory_format=torch.channels_last)
     gy = torch.randn(2, 256, 24, 40, device=dev).half().contiguous(memory_format=torch.channels_last)
     grads = []
-    for xsum in (None, ({}, "give")):
+    for links in (HF.NO_LINKS, HF.Links(shared=HF.SharedInputLink(), gives=True)):
         src = x0.clone().requires_grad_(True)
         with torch.autocast("cuda", dtype=torch.float16):
-            y = HF.conv_nhwc(src * 1.0, conv, xsum=xsum)
+            y = HF.conv_nhwc(src * 1.0, conv, links=links)
         y.backward(gy)
         assert src.grad is not None and float(src.grad.abs().max()) > 0
         grads.append(src.grad.clone())
     assert torch.equal(grads[0], grads[1])
     # ... and with a registered taker the pair still delivers ONE summed gradient (tests/test_gpu_round4.py covers the values)
-    xs = {}
+    xs = HF.SharedInputLink()
     src = x0.clone().requires_grad_(True)
     xin = src * 1.0
     conv_t = nn.Conv2d(512, 256, 1, bias=False).to(dev)
     with torch.autocast("cuda", dtype=torch.float16):
-        yt = HF.conv_nhwc(xin, conv_t, xsum=(xs, "take"))
-        yg = HF.conv_nhwc(xin, conv, xsum=(xs, "give"))
-    assert xs.get("taker") is True
+        yt = HF.conv_nhwc(xin, conv_t, links=HF.Links(shared=xs))
+        yg = HF.conv_nhwc(xin, conv, links=HF.Links(shared=xs, gives=True))
+    assert xs.taker is True
     (yg.float() * gy.float()).sum().add((yt.float() * gy.float()).sum()).backward()
     ref = x0.clone().requires_grad_(True)
     with torch.autocast("cuda", dtype=torch.float16):

@@ -7,7 +7,8 @@ import os
 def test_switches_are_read_once_at_import(monkeypatch):
     from hiast_amd import switches as SW
     assert set(SW.SWITCHES) == {"HIAST_NO_BN_MASK", "HIAST_NO_BN_BWD_FUSION", "HIAST_LIB_WGRAD", "HIAST_NO_WGROUP",
-                                "HIAST_NO_XSUM", "HIAST_NO_IDT_HANDOFF", "HIAST_LIB_STEM"}
+                                "HIAST_NO_XSUM", "HIAST_NO_IDT_HANDOFF", "HIAST_LIB_STEM", "HIAST_NO_BN3_FUSION",
+                                "HIAST_LIB_DGRAD_S2", "HIAST_NO_ASYNC_STAT"}
     before = dict(SW.SWITCHES)
     monkeypatch.setenv("HIAST_NO_XSUM", "0" if before["HIAST_NO_XSUM"] else "1")
     assert SW.on("HIAST_NO_XSUM") == before["HIAST_NO_XSUM"]          # the environment is not consulted again
