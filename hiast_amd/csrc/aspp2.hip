@@ -398,7 +398,7 @@ extern "C" int hiast_aspp2_fwd(const void* x_nhwc, int dtype, const void* wt, co
     static const bool t32 = [] { const char* v = getenv("HIAST_ASPP_T32"); return v && atoi(v) != 0; }();
     const bool t16 = dtype == HIAST_FMT_FP16 && !t32;
     if (dtype == 0)      // fp32 rows, fp32 weights: the register-staged kernel splits on the fly
-        e = hiast_gemm_nt_launch(x_nhwc, (const float*)wt, T, M, Cin, NP, 0, st);
+        e = hiast_gemm_nt_launch((const float*)x_nhwc, (const float*)wt, T, M, Cin, NP, st);
     else {               // bf16 rows (1) / split planes (2) / fp16 rows (3), weights packed by hiast_pack_conv_weight: LDS-DMA kernel
         ConvLaunch c;
         c.x = x_nhwc; c.wp = wt; c.y = T;

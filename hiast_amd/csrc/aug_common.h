@@ -1,7 +1,9 @@
 // What the kernels of the device-side sample path (sample_aug.hip K15, sample_aug2.hip K15b, sample_aug3.hip K15c) agree
 // on, defined once: the words of a view's op row, the segment record the host cuts a row into (hiast_hip.h, K15b), the
-// 12-byte form of four HWC pixels and the grid of a pass over pixels.  gfx950 only.
+// 12-byte form of four HWC pixels and the grid of a pass over pixels.  gfx950 only.  The words and kinds of a sample's
+// record row are host-safe and live in aug_records.h.
 #pragma once
+#include "aug_records.h"
 #include "common.h"
 
 namespace hiast {

@@ -1,13 +1,15 @@
-// Stand-alone host program around aug_mix_host.h (no device code, no HIP runtime): builds the smallest batch of record
+// Stand-alone host program around aug_records.h (no device code, no HIP runtime): builds the smallest batch of record
 // kinds 3 and 4 as device_aug.build_batch_tables lays it out and runs the bounds checks over it and over broken copies.
 // Meant for a host sanitizer build:  make -C hiast_amd/csrc sanitize-host
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "aug_mix_host.h"
+#include "aug_records.h"
 
 namespace {
+
+using namespace hiast;
 
 int failures = 0;
 
@@ -36,22 +38,24 @@ Batch smallest()
 {
     Batch b;
     const int ch = 2, cw = 3;
-    b.recs.assign(2 * HIAST_AUG_REC_WORDS, -1);
+    b.recs.assign(2 * REC, -1);
     const int64_t img = 0, lbl = 32, pimg = 48, plbl = 80, tab0 = 96, tab1 = tab0 + 272;
     b.blob.assign((size_t)tab1 + HIAST_MIX_TABLE_BYTES, 1);
     int64_t* r = b.recs.data();
-    r[0] = HIAST_MIX_KIND_PLAN_RECT, r[1] = img, r[2] = lbl, r[3] = pimg, r[4] = plbl, r[5] = tab0, r[6] = ch, r[7] = cw, r[8] = 0;
+    r[R_KIND] = KIND_PLAN_RECT, r[R_IMG] = img, r[R_LBL] = lbl, r[R_PIMG] = pimg, r[R_PLBL] = plbl, r[R_PTAB] = tab0;
+    r[R_CH] = ch, r[R_CW] = cw, r[R_FLIP] = 0;
     put_rect(b, tab0, 0, 1, 1, 3);
-    r += HIAST_AUG_REC_WORDS;
-    r[0] = HIAST_MIX_KIND_STORE_RECT, r[1] = 300, r[2] = 1000, r[3] = 2300, r[4] = 3000, r[5] = tab1, r[6] = ch, r[7] = cw, r[8] = 1;
-    r[HIAST_STORE_REC_STRIDE] = 40;
+    r += REC;
+    r[R_KIND] = KIND_STORE_RECT, r[R_IMG] = 300, r[R_LBL] = 1000, r[R_PIMG] = 2300, r[R_PLBL] = 3000, r[R_PTAB] = tab1;
+    r[R_CH] = ch, r[R_CW] = cw, r[R_FLIP] = 1;
+    r[R_STRIDE] = 40;
     put_rect(b, tab1, 0, 0, 0, 0);       // empty
     return b;
 }
 
 int check(const Batch& b, int max_kind)
 {
-    return hiast_mix_host::check_records(b.recs.data(), b.blob.data(), (int64_t)b.blob.size(), 2, max_kind);
+    return hiast_aug_host::check_records(b.recs.data(), b.blob.data(), (int64_t)b.blob.size(), 2, max_kind);
 }
 
 }  // namespace
@@ -63,13 +67,13 @@ int main()
     expect(check(ok, 2), HIAST_E_ARG, "kinds 3 and 4 through hiast_aug_geometry_store_u8");
     expect(check(ok, 1), HIAST_E_ARG, "kinds 3 and 4 through hiast_aug_geometry_u8");
     expect(check(ok, 5), HIAST_E_ARG, "a max_kind the ABI does not have");
-    expect(hiast_mix_host::check_records(nullptr, ok.blob.data(), (int64_t)ok.blob.size(), 2, 4), HIAST_E_ARG, "null records");
-    expect(hiast_mix_host::check_records(ok.recs.data(), nullptr, 0, 2, 4), HIAST_E_ARG, "a rectangle kind without a blob");
+    expect(hiast_aug_host::check_records(nullptr, ok.blob.data(), (int64_t)ok.blob.size(), 2, 4), HIAST_E_ARG, "null records");
+    expect(hiast_aug_host::check_records(ok.recs.data(), nullptr, 0, 2, 4), HIAST_E_ARG, "a rectangle kind without a blob");
     const int32_t bad[][4] = {{0, 3, 0, 3}, {0, 2, 0, 4}, {-1, 2, 0, 3}, {2, 1, 0, 3}, {0, 2, 3, 2}, {0, 2, -2, 3}};
     for (const auto& q : bad)
         for (int s = 0; s < 2; ++s) {
             Batch b = smallest();
-            put_rect(b, b.recs[(size_t)s * HIAST_AUG_REC_WORDS + 5], q[0], q[1], q[2], q[3]);
+            put_rect(b, b.recs[(size_t)s * REC + R_PTAB], q[0], q[1], q[2], q[3]);
             expect(check(b, 4), HIAST_E_ARG, "a rectangle outside [0, ch] x [0, cw] or reversed");
         }
     for (size_t cut = 1; cut <= 16; cut += 3) {       // a blob too short for the last table + 16 bytes
@@ -86,26 +90,26 @@ int main()
     }
     for (int64_t off : {(int64_t)-4, (int64_t)98, (int64_t)1 << 40, INT64_MAX - 8, INT64_MIN}) {
         Batch b = smallest();
-        b.recs[5] = off;
+        b.recs[R_PTAB] = off;
         expect(check(b, 4), HIAST_E_ARG, "a table offset that is negative, unaligned or far outside");
     }
-    for (int w : {3, 4, 6, 7}) {
+    for (int w : {R_PIMG, R_PLBL, R_CH, R_CW}) {
         Batch b = smallest();
-        b.recs[HIAST_AUG_REC_WORDS + w] = (w < 6) ? -1 : 0;
+        b.recs[REC + w] = (w == R_PIMG || w == R_PLBL) ? -1 : 0;
         expect(check(b, 4), HIAST_E_ARG, "a rectangle kind without a paste source / with an empty window");
     }
     {
         Batch b = smallest();
-        b.recs[0] = 0, b.recs[HIAST_AUG_REC_WORDS] = 2;      // the same rows as kinds 0 and 2: nothing behind the table is read
+        b.recs[R_KIND] = KIND_PLAN, b.recs[REC + R_KIND] = KIND_STORE;      // the same rows as kinds 0 and 2: nothing behind the table is read
         b.blob.resize(96 + 256);
         b.blob.shrink_to_fit();
         expect(check(b, 2), 0, "kinds 0 and 2");
-        b.recs[0] = 7;
+        b.recs[R_KIND] = 7;
         expect(check(b, 4), HIAST_E_ARG, "an unknown kind");
-        b.recs[0] = -1;
+        b.recs[R_KIND] = -1;
         expect(check(b, 4), HIAST_E_ARG, "a negative kind");
     }
     if (failures) return 1;
-    std::puts("aug_mix_check: ok");
+    std::puts("aug_records_check: ok");
     return 0;
 }

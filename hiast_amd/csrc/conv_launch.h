@@ -88,4 +88,4 @@ int hiast_xconv_launch(const ConvLaunch& c, const ConvRoute& r);
 int hiast_xconv2_ok(const ConvLaunch& c);
 int hiast_xconv2_launch(const ConvLaunch& c);
 // conv1x1.hip: fp32 rows x fp32 weights (the ASPP tap GEMM on unpacked operands)
-int hiast_gemm_nt_launch(const void* x, const float* w, void* y, int64_t M, int K, int N, int dtype, hipStream_t st);
+int hiast_gemm_nt_launch(const float* x, const float* w, float* y, int64_t M, int K, int N, hipStream_t st);

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import aug_records as _R
 from . import switches as _SW
 from ._lib import NBINS, check
 
@@ -708,22 +709,17 @@ def multi_copy(plan):
 
 
 # ------------------------------------------------------------------------------- K15 device-side sample path
-AUG_REC_WORDS, AUG_MAX_OPS = 20, 8
-AUG_OPS_WORDS = 4 + 2 * AUG_MAX_OPS
-AUG_MAX_KSIZE = 41
-# op types of a view's row (include/hiast_hip.h HIAST_AUG_OP_*, device_aug.OP_*)
-AUG_OP_LUT, AUG_OP_GRAY, AUG_OP_EQUALIZE, AUG_OP_CONTRAST, AUG_OP_SAT, AUG_OP_HUE, AUG_OP_BLUR, AUG_OP_FDA = range(1, 9)
+# the words, kinds and op types of the tables are hiast_amd/aug_records.py's (_R); the AUG_* names are aliases
+AUG_REC_WORDS, AUG_MAX_OPS, AUG_OPS_WORDS, AUG_MAX_KSIZE = _R.REC_WORDS, _R.MAX_OPS, _R.OPS_WORDS, _R.MAX_KSIZE
+AUG_OP_LUT, AUG_OP_GRAY, AUG_OP_EQUALIZE, AUG_OP_CONTRAST = _R.OP_LUT, _R.OP_GRAY, _R.OP_EQUALIZE, _R.OP_CONTRAST
+AUG_OP_SAT, AUG_OP_HUE, AUG_OP_BLUR, AUG_OP_FDA = _R.OP_SAT, _R.OP_HUE, _R.OP_BLUR, _R.OP_FDA
 AUG_LEVEL1_OPS = (AUG_OP_LUT, AUG_OP_GRAY, AUG_OP_EQUALIZE)
 AUG_TABLE_OPS = (AUG_OP_EQUALIZE, AUG_OP_CONTRAST)        # a table built from the whole image: at most one per segment
 AUG_CLOSING_OPS = (AUG_OP_BLUR, AUG_OP_FDA)                # launches of their own after a segment's colour pass
-AUG_FDA_MAX_BORDER, AUG_FDA_BORDER_SHIFT, AUG_FDA_MIN_SIDE = 2, 40, 8
-
-
-AUG_KIND_STORE, AUG_REC_STRIDE = 2, 19                   # include/hiast_hip.h HIAST_STORE_KIND, HIAST_STORE_REC_STRIDE
-# a kind 0 / kind 2 record whose paste is confined to a rectangle: its paste table is followed by ry0, ry1, rx0, rx1 (int32,
-# window coordinates); include/hiast_hip.h HIAST_MIX_KIND_PLAN_RECT, HIAST_MIX_KIND_STORE_RECT, HIAST_MIX_TABLE_BYTES
-AUG_KIND_PLAN_RECT, AUG_KIND_STORE_RECT, AUG_MIX_TABLE_BYTES = 3, 4, 256 + 16
-AUG_RECT_KINDS = (AUG_KIND_PLAN_RECT, AUG_KIND_STORE_RECT)
+AUG_FDA_MAX_BORDER, AUG_FDA_BORDER_SHIFT, AUG_FDA_MIN_SIDE = _R.FDA_MAX_BORDER, _R.FDA_BORDER_SHIFT, _R.FDA_MIN_SIDE
+AUG_KIND_STORE, AUG_REC_STRIDE = _R.KIND_STORE, _R.R_STRIDE
+AUG_KIND_PLAN_RECT, AUG_KIND_STORE_RECT, AUG_MIX_TABLE_BYTES = _R.KIND_PLAN_RECT, _R.KIND_STORE_RECT, _R.MIX_TABLE_BYTES
+AUG_RECT_KINDS = _R.RECT_KINDS
 
 
 def _aug_check_store_windows(r, b, store):
@@ -870,52 +866,27 @@ def _aug_records_check(host, max_kind, entry):
         check(rc, entry)
 
 
-def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch, store=None, host=None):
-    """device tensors of one batch (blob uint8, tabs int32, recs int64 [B, 20]: include/hiast_hip.h, K15; ALREADY bounds-
-    checked by the caller) -> (uint8 [B, oh, ow, 3], uint8 label [B, oh, ow]): CopyPaste select, flip, crop, Pillow's
-    two-pass 8-bit resample and the nearest label gather, byte for byte.  store: the uint8 buffer of device-resident
-    frames that records of kind 2 address (hiast_aug_geometry_store_u8).  host: the host copies (recs, blob) — with them
-    a record kind these entries do not know (3, 4; 2 without a store) is refused with HIAST_E_ARG before anything is
-    allocated or launched"""
+# the three C entries of the geometry pass run the same two kernels: entry -> (highest record kind it knows, takes a store)
+_AUG_GEOMETRY_ENTRIES = {"hiast_aug_geometry_u8": (_R.KIND_FINISHED, False),
+                         "hiast_aug_geometry_store_u8": (_R.KIND_STORE, True),
+                         "hiast_aug_geometry_mix_u8": (_R.KIND_STORE_RECT, True)}
+
+
+def _aug_geometry(name, entry, blob, tabs, recs, oh, ow, max_ch, store=None, host=None, out=None):
+    """the one body of aug_geometry_u8 / aug_geometry_mix_u8 (name: the wrapper, for its error texts)"""
+    max_kind, takes_store = _AUG_GEOMETRY_ENTRIES[entry]
+    assert takes_store or store is None
     _req(blob, torch.uint8, 1, "blob")
     _req(tabs, torch.int32, 1, "tabs")
     _req(recs, torch.int64, 2, "recs")
     if host is not None:
-        _aug_records_check(host, 1 if store is None else AUG_KIND_STORE,
-                           "hiast_aug_geometry_u8" if store is None else "hiast_aug_geometry_store_u8")
-    B = recs.shape[0]
-    dev = blob.device
-    tmp = torch.empty((B, max_ch, ow, 3), dtype=torch.uint8, device=dev)
-    img = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=dev)
-    lbl = torch.empty((B, oh, ow), dtype=torch.uint8, device=dev)
-    if store is not None:
-        _req(store, torch.uint8, 1, "store")
-        if store.device != dev or store.numel() == 0:
-            raise ValueError("aug_geometry_u8: the store must be a non-empty buffer on the batch's device")
-        check(_lib.load().hiast_aug_geometry_store_u8(_ptr(recs), _ptr(blob), _ptr(store), _ptr(tabs), _ptr(tmp), _ptr(img),
-                                                      _ptr(lbl), B, max_ch, oh, ow, _stream()), "hiast_aug_geometry_store_u8")
-        return img, lbl
-    check(_lib.load().hiast_aug_geometry_u8(_ptr(recs), _ptr(blob), _ptr(tabs), _ptr(tmp), _ptr(img), _ptr(lbl), B, max_ch,
-                                            oh, ow, _stream()), "hiast_aug_geometry_u8")
-    return img, lbl
-
-
-def aug_geometry_mix_u8(blob, tabs, recs, oh, ow, max_ch, store=None, host=None, out=None):
-    """aug_geometry_u8 for batches that may hold every record kind 0..4 (hiast_aug_geometry_mix_u8): kinds 3 and 4 confine
-    the paste to the rectangle behind their table (ClassMix has none, CutMix has one).  store may be None when no record
-    is of kind 2 or 4.  host: as for aug_geometry_u8 (kinds 0..4, and every rectangle inside its window).  out: (tmp, img,
-    lbl) to write into instead of fresh tensors (uint8, of B*max_ch*ow*3, B*oh*ow*3 and B*oh*ow elements)"""
-    _req(blob, torch.uint8, 1, "blob")
-    _req(tabs, torch.int32, 1, "tabs")
-    _req(recs, torch.int64, 2, "recs")
-    if host is not None:
-        _aug_records_check(host, AUG_KIND_STORE_RECT, "hiast_aug_geometry_mix_u8")
+        _aug_records_check(host, max_kind, entry)
     B = recs.shape[0]
     dev = blob.device
     if store is not None:
         _req(store, torch.uint8, 1, "store")
         if store.device != dev or store.numel() == 0:
-            raise ValueError("aug_geometry_mix_u8: the store must be a non-empty buffer on the batch's device")
+            raise ValueError("%s: the store must be a non-empty buffer on the batch's device" % name)
     if out is None:
         tmp = torch.empty((B, max_ch, ow, 3), dtype=torch.uint8, device=dev)
         img = torch.empty((B, oh, ow, 3), dtype=torch.uint8, device=dev)
@@ -924,12 +895,30 @@ def aug_geometry_mix_u8(blob, tabs, recs, oh, ow, max_ch, store=None, host=None,
         tmp, img, lbl = out
         for t, n, nm in ((tmp, B * max_ch * ow * 3, "tmp"), (img, B * oh * ow * 3, "img"), (lbl, B * oh * ow, "lbl")):
             if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous() or t.numel() != n:
-                raise ValueError("aug_geometry_mix_u8: %s must be a contiguous uint8 tensor of %d elements on the batch's device"
-                                 % (nm, n))
-    check(_lib.load().hiast_aug_geometry_mix_u8(_ptr(recs), _ptr(blob), 0 if store is None else _ptr(store), _ptr(tabs),
-                                                _ptr(tmp), _ptr(img), _ptr(lbl), B, max_ch, oh, ow, _stream()),
-          "hiast_aug_geometry_mix_u8")
+                raise ValueError("%s: %s must be a contiguous uint8 tensor of %d elements on the batch's device" % (name, nm, n))
+    args = [_ptr(recs), _ptr(blob)] + ([_ptr(store)] if takes_store else []) + [_ptr(tabs), _ptr(tmp), _ptr(img), _ptr(lbl)]
+    check(getattr(_lib.load(), entry)(*args, B, max_ch, oh, ow, _stream()), entry)
     return img, lbl
+
+
+def aug_geometry_u8(blob, tabs, recs, oh, ow, max_ch, store=None, host=None):
+    """device tensors of one batch (blob uint8, tabs int32, recs int64 [B, 20]: include/hiast_hip.h, K15; ALREADY bounds-
+    checked by the caller) -> (uint8 [B, oh, ow, 3], uint8 label [B, oh, ow]): CopyPaste select, flip, crop, Pillow's
+    two-pass 8-bit resample and the nearest label gather, byte for byte.  store: the uint8 buffer of device-resident
+    frames that records of kind 2 address (hiast_aug_geometry_store_u8).  host: the host copies (recs, blob) — with them
+    a record kind these entries do not know (3, 4; 2 without a store) is refused with HIAST_E_ARG before anything is
+    allocated or launched; without them the kernels leave such a record's rows of the outputs unwritten"""
+    entry = "hiast_aug_geometry_u8" if store is None else "hiast_aug_geometry_store_u8"
+    return _aug_geometry("aug_geometry_u8", entry, blob, tabs, recs, oh, ow, max_ch, store=store, host=host)
+
+
+def aug_geometry_mix_u8(blob, tabs, recs, oh, ow, max_ch, store=None, host=None, out=None):
+    """aug_geometry_u8 for batches that may hold every record kind 0..4 (hiast_aug_geometry_mix_u8): kinds 3 and 4 confine
+    the paste to the rectangle behind their table (ClassMix has none, CutMix has one).  store may be None when no record
+    is of kind 2 or 4.  host: as for aug_geometry_u8 (kinds 0..4, and every rectangle inside its window).  out: (tmp, img,
+    lbl) to write into instead of fresh tensors (uint8, of B*max_ch*ow*3, B*oh*ow*3 and B*oh*ow elements)"""
+    return _aug_geometry("aug_geometry_mix_u8", "hiast_aug_geometry_mix_u8", blob, tabs, recs, oh, ow, max_ch, store=store,
+                         host=host, out=out)
 
 
 def paste_mask_u8(store, blob, prm, out):

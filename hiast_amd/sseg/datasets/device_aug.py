@@ -35,17 +35,16 @@ import random
 import numpy as np
 import torch
 
+# the words, kinds and op types of the hand-over tables: defined once, in hiast_amd/aug_records.py
+from hiast_amd.aug_records import (  # noqa: F401  (re-exported: callers and tests read them as device_aug.R_KIND, ...)
+    FDA_BORDER_SHIFT, FDA_MAX_BORDER, FDA_MIN_SIDE, KIND_FINISHED, KIND_PLAN, KIND_PLAN_RECT, KIND_STORE, KIND_STORE_RECT,
+    MAX_KSIZE, MAX_OPS, MIX_TABLE_BYTES, OP_BLUR, OP_CONTRAST, OP_EQUALIZE, OP_FDA, OP_GRAY, OP_HUE, OP_LUT, OP_SAT, OPS_WORDS,
+    R_CH, R_CW, R_FLIP, R_HK, R_HLO, R_HN, R_HT, R_IMG, R_KIND, R_LBL, R_NX, R_NY, R_PIMG, R_PLBL, R_PTAB, R_STRIDE, R_VK,
+    R_VLO, R_VN, R_VT, REC_WORDS, RECT_BYTES, RECT_KINDS)
 from hiast_amd.sseg.datasets import augmentations as A
 
 PRECISION_BITS = 22          # Pillow: 32 - 8 - 2
-MAX_OPS = 8                  # colour ops per view the device record holds (after composing neighbouring LUTs)
 HOST_ONLY = (A.ColorJitter, A.GaussianBlur, A.FDA)
-
-OP_LUT, OP_GRAY, OP_EQUALIZE = 1, 2, 3
-OP_CONTRAST, OP_SAT, OP_HUE, OP_BLUR = 4, 5, 6, 7        # level 2 (plan_sample(level=2)): ColorJitter's steps, GaussianBlur
-MAX_KSIZE = 41
-OP_FDA = 8                                               # level 3: blob offset of the target view | border << 40
-FDA_MAX_BORDER, FDA_BORDER_SHIFT, FDA_MIN_SIDE = 2, 40, 8
 
 
 # ------------------------------------------------------------------------------------------------- tables
@@ -637,18 +636,8 @@ def execute_plan_host(plan, img, lbl, paste=None, sliced=False):
 
 
 # ------------------------------------------------------------------------------------------------- hand-over
-# one int64 record row per sample (offsets into the batch's uint8 blob / int32 table blob)
-R_KIND, R_IMG, R_LBL, R_PIMG, R_PLBL, R_PTAB, R_CH, R_CW, R_FLIP, R_HLO, R_HN, R_HK, R_HT, R_VLO, R_VN, R_VK, R_VT, R_NX, \
-    R_NY = range(19)
-R_STRIDE = 19                # KIND_STORE: the frame's width in pixels, the row stride of a window read in place
-REC_WORDS = 20
-# per (view, sample): kind, offset of the finished view, n ops, then (type, blob offset of the table) x MAX_OPS
-OPS_WORDS = 4 + 2 * MAX_OPS
-KIND_PLAN, KIND_FINISHED, KIND_STORE = 0, 1, 2
-# kind 0 / kind 2 whose paste is confined to a rectangle (CutMix): the paste table's 256 bytes are followed by ry0, ry1, rx0,
-# rx1 as little-endian int32 in WINDOW coordinates, clipped (an empty rectangle has ry0 == ry1)
-KIND_PLAN_RECT, KIND_STORE_RECT = 3, 4
-RECT_BYTES = 16
+# one int64 record row per sample (offsets into the batch's uint8 blob / int32 table blob) and one op row per (view, sample):
+# their words (R_*, REC_WORDS, OPS_WORDS) and kinds (KIND_*) are hiast_amd/aug_records.py's
 
 
 def paste_table_bytes(table, rect_w=None):

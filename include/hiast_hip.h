@@ -557,7 +557,13 @@ int hiast_normalize_u8(const uint8_t* img, float* out, int B, int64_t HW, const 
  *        (0, n_ops, index of its Equalize | -1, -1).
  * hiast_aug_geometry_u8: CopyPaste select on load (table[paste_lbl] ? paste : own), flipped read, horizontal pass into
  *   tmp [B][max_ch][ow][3] (rounded to uint8), vertical pass -> img_out uint8 [B][oh][ow][3]; label gather through the
- *   same select -> lbl_out uint8 [B][oh][ow].  Two launches. */
+ *   same select -> lbl_out uint8 [B][oh][ow].  Two launches.
+ * The three geometry entries (hiast_aug_geometry_u8, _store_u8 and _mix_u8 below) run the SAME two kernels and differ in
+ *   three things only: the highest record kind they know (max_kind 1, 2, 4), whether `store` may be null (no such argument,
+ *   never, always) and what they ask of `blob` (any address, any address, 4-byte aligned).  A record whose kind is above
+ *   the entry's max_kind, or is a store kind (2, 4) while `store` is null, is LEFT ALONE by both launches: nothing is read
+ *   through its offsets, and its rows of tmp, img_out and lbl_out are not written.  The vertical pass moves 4 bytes per
+ *   lane exactly when ow * 3 is a multiple of 4 and tmp, img_out and blob are 4-byte aligned, single bytes otherwise. */
 #define HIAST_AUG_REC_WORDS 20
 #define HIAST_AUG_MAX_OPS 8
 #define HIAST_AUG_OPS_WORDS (4 + 2 * HIAST_AUG_MAX_OPS)
@@ -575,7 +581,8 @@ int hiast_aug_geometry_u8(const int64_t* recs, const uint8_t* blob, const int32_
  *   (y1 * W + x1) * 3 for an image, + y1 * W + x1 for a label —, record word HIAST_STORE_REC_STRIDE (19, spare in the
  *   other kinds) is the frame's width W in pixels = the row stride (>= cw); paste_table and every tap / nearest table
  *   stay in blob / tabs.  The arithmetic is that of kind 0 (which reads the same window with row stride cw); kinds 0, 1
- *   and 2 may be mixed in one batch.  hiast_aug_geometry_u8 itself knows kinds 0 and 1 only.
+ *   and 2 may be mixed in one batch; a null `store` is HIAST_E_ARG.  hiast_aug_geometry_u8 itself knows kinds 0 and 1
+ *   only (a record of kind 2 is left alone there, see K15).
  * hiast_normalize_gather_u8: hiast_normalize_u8 on B frames of HW pixels that start at store + offsets[b] (offsets:
  *   DEVICE int64 [B]) -> out float32 [B][3][HW], one launch, the same operations in the same order (bit-identical to
  *   hiast_normalize_u8 on the same bytes).  mean / std: HOST float[3].
@@ -599,10 +606,11 @@ int hiast_normalize_gather_u8(const uint8_t* store, const int64_t* offsets, floa
  *   arithmetic; the select on load is table[paste_lbl] && ry0 <= row < ry1 && rx0 <= col < rx1 in the horizontal pass and
  *   in the label gather (kinds 0 and 2: the table alone).  A row outside the rectangle reads no byte of the paste source,
  *   a column outside it neither.  `store` may be NULL when no record is of kind 2 or 4 (such a record is then left
- *   unwritten).  `blob` must be 4-byte aligned.
- *   hiast_aug_geometry_u8 / hiast_aug_geometry_store_u8 know kinds 0..2 only.  Records live on the device, so no launch
- *   entry can read a kind: the refusal is hiast_aug_records_check on the HOST copy, which the wrappers
- *   (hiast_amd/kernels.py) call before every geometry entry with that entry's max_kind.
+ *   alone).  `blob` must be 4-byte aligned (HIAST_E_ARG otherwise: the rectangle is read as int32).
+ *   hiast_aug_geometry_u8 / hiast_aug_geometry_store_u8 know kinds 0..1 / 0..2 only and leave a record of a higher kind
+ *   alone (K15: the unknown-kind rule).  Records live on the device, so no launch entry can REFUSE a kind: the refusal is
+ *   hiast_aug_records_check on the HOST copy, which the wrappers (hiast_amd/kernels.py) call before every geometry entry
+ *   with that entry's max_kind.
  * hiast_aug_records_check: HOST recs [B][HIAST_AUG_REC_WORDS] and HOST blob of blob_bytes -> 0, or HIAST_E_ARG for a kind
  *   outside 0..max_kind (max_kind: 1, 2 or 4), and for a record of kind 3 / 4 without paste offsets, whose table +
  *   rectangle is not inside the blob at a multiple of 4, or whose rectangle leaves [0, ch] x [0, cw] or has y0 > y1 or

@@ -206,6 +206,55 @@ def test_kinds_0_to_4_in_one_batch_and_kinds_0_to_2_through_both_entries(K, fram
     assert np.array_equal(views[0].cpu().numpy(), got_i) and np.array_equal(lbl.cpu().numpy(), got_l)
 
 
+UNKNOWN = {"hiast_aug_geometry_u8": (2, 3, 4), "hiast_aug_geometry_store_u8": (3, 4), "hiast_aug_geometry_mix_u8": (2, 4)}
+
+
+@pytest.mark.parametrize("out", [(5, 9), (8, 12)])          # the 1-byte and the 4-byte form of the vertical pass
+@pytest.mark.parametrize("entry", sorted(UNKNOWN))
+def test_a_record_kind_the_entry_does_not_know_is_left_alone(K, frames, store, entry, out):
+    """the C entries themselves, no host check in front: one sample of a kind the entry knows beside one of every kind it does
+    not (for hiast_aug_geometry_mix_u8: the store kinds, with a null store).  The unknown samples' rows of tmp, img_out and
+    lbl_out keep their prefill, the known sample is the numpy executor's, the guard bands are intact.  The blob is padded so
+    that every offset of an unknown record, taken for a blob offset, has a whole window and oh*ow*3 bytes behind it: a kernel
+    that mistakes such a record for another kind fails by bytes, not by a fault"""
+    from hiast_amd import _lib
+    tab, rect, fill = _table("half"), (4, 9, 8, 30), 0xA5
+    wins = [WINDOWS[0], (0, 20, 0, 45)]                                     # 7 x 13 and 20 x 45 (store row stride 45)
+    plans = [_plan(wins[k % 2], out, bool(k % 2)) for k in range(4)]
+    make = {0: lambda p: _bytes_sample(frames, p, 0, 1, tab, None), 2: lambda p: _store_sample(store, p, 0, 1, tab, None),
+            3: lambda p: _bytes_sample(frames, p, 0, 1, tab, rect), 4: lambda p: _store_sample(store, p, 0, 1, tab, rect)}
+    known = {"hiast_aug_geometry_u8": 0, "hiast_aug_geometry_store_u8": 2, "hiast_aug_geometry_mix_u8": 3}[entry]
+    kinds = (known,) + UNKNOWN[entry]
+    t = DA.build_batch_tables([make[k](p) for k, p in zip(kinds, plans)])
+    assert t["recs"][:, DA.R_KIND].tolist() == list(kinds)
+    _, oh, ow, max_ch, _ = (int(v) for v in t["meta"])
+    assert (oh, ow) == out and max_ch == 20
+    B = len(kinds)
+    reach = int(t["recs"][1:, DA.R_IMG:DA.R_PTAB + 1].max()) + 20 * 45 * 3 + oh * ow * 3 + DA.MIX_TABLE_BYTES
+    pad = (torch.arange(max(0, reach - t["blob"].numel())) % 160).to(torch.uint8)       # (never the prefill's value)
+    blob_d = torch.cat([t["blob"], pad]).cuda()
+    assert blob_d.data_ptr() % 4 == 0
+    tabs_d, recs_d = t["tabs"].cuda(), t["recs"].cuda()
+    carved = [G.carve(s, torch.uint8, "cuda", BAND) for s in ((B, max_ch, ow, 3), (B, oh, ow, 3), (B, oh, ow))]
+    for c, _ in carved:
+        c.fill_(fill)
+    tmp, img, lbl = (c for c, _ in carved)
+    stores = {"hiast_aug_geometry_u8": (), "hiast_aug_geometry_store_u8": (store.buffer.data_ptr(),),
+              "hiast_aug_geometry_mix_u8": (0,)}[entry]
+    rc = getattr(_lib.load(), entry)(recs_d.data_ptr(), blob_d.data_ptr(), *stores, tabs_d.data_ptr(), tmp.data_ptr(),
+                                     img.data_ptr(), lbl.data_ptr(), B, max_ch, oh, ow, K._stream())
+    torch.cuda.synchronize()
+    assert rc == 0
+    for (_, h), what in zip(carved, ("tmp", "img_out", "lbl_out")):
+        G.check(h, what)
+    for b in range(1, B):
+        for c, what in zip((tmp, img, lbl), ("tmp", "img_out", "lbl_out")):
+            assert int((c[b] != fill).sum()) == 0, (what, "written for the unknown kind", kinds[b])
+    w_i, w_l = _want(frames, plans[0], 0, 1, tab, rect if known == 3 else None)
+    assert np.array_equal(img[0].cpu().numpy(), w_i) and np.array_equal(lbl[0].cpu().numpy(), w_l)
+    assert int((tmp[0, :7] != fill).sum()) > 0                              # (and the known sample went through tmp)
+
+
 def test_refusals_launch_nothing(K, frames, store):
     from hiast_amd import _lib
     tab, rect = _table("half"), (4, 9, 8, 30)
