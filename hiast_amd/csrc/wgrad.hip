@@ -367,14 +367,14 @@ __global__ __launch_bounds__(512) void wgrad_group_kernel(const WGroup g)
         wgrad_tn_body<9, F16, false>(smem, jb.dY, jb.X, jb.P, jb.M, jb.N, jb.K, jb.geo, jb.m_per_split, t, split);
 }
 
-// dW[n][k][tap] (torch [N][K][kh][kw]) = Σ_s P[s][n][tap][k], ascending s (fixed order: bitwise reproducible).
-// thread = (n, tap, 4 consecutive k): the partials are read as they lie — 16 bytes per lane, eight splits in flight
-// (the first form, one float per thread and four loads in flight, streamed the 67 MB of a layer3 1x1 at 1.8 TB/s:
-// 38 us x 81 launches per training step) — only the small result is written with the tap stride.
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ P, float* __restrict__ dw, int N,
-                                                           int K, int taps, int nsplit)
+// dW[n][k][tap] (torch [N][K][kh][kw]) = Σ_s P[s][n][tap][k], ascending s (fixed order: bitwise reproducible) — THE reduction
+// of both launch forms.  thread = (n, tap, 4 consecutive k), idx4 = its float4 index along [n][tap][k]: the partials are read
+// as they lie — 16 bytes per lane, eight splits in flight (the first form, one float per thread and four loads in flight,
+// streamed the 67 MB of a layer3 1x1 at 1.8 TB/s: 38 us x 81 launches per training step) — only the small result is written
+// with the tap stride.
+__device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ P, float* __restrict__ dw, int N, int K, int taps,
+                                                  int nsplit, long long idx4)
 {
-    const long long idx4 = (long long)blockIdx.x * 256 + threadIdx.x;       // index of a float4 along [n][tap][k]
     const size_t per = (size_t)N * taps * K;
     if (idx4 * 4 >= (long long)per) return;
     const long long idx = idx4 * 4;
@@ -406,46 +406,22 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
-// the same reduction for every job of a grouped launch in ONE grid (f4_begin: first float4 index of a job's [n][tap][k])
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ P, float* __restrict__ dw, int N,
+                                                           int K, int taps, int nsplit)
+{
+    wgrad_reduce_body(P, dw, N, K, taps, nsplit, (long long)blockIdx.x * 256 + threadIdx.x);
+}
+
+// every job of a grouped launch in ONE grid (f4_begin: first float4 index of a job's [n][tap][k])
 __global__ __launch_bounds__(256) void wgrad_group_reduce_kernel(const WGroup g)
 {
-    long long idx4 = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long idx4 = (long long)blockIdx.x * 256 + threadIdx.x;
     int ji = 0;
 #pragma unroll
     for (int q = 1; q < WG_MAXJOBS; ++q)
         if (q < g.njobs && idx4 >= g.j[q].f4_begin) ji = q;
     const WJob& jb = g.j[ji];
-    idx4 -= jb.f4_begin;
-    const int N = jb.N, K = jb.K, taps = jb.taps, nsplit = jb.nsplit;
-    const size_t per = (size_t)N * taps * K;
-    if (idx4 * 4 >= (long long)per) return;
-    const long long idx = idx4 * 4;
-    const int k = (int)(idx % K);
-    const long long nt = idx / K;
-    const int t = (int)(nt % taps), n = (int)(nt / taps);
-    const float4* p = reinterpret_cast<const float4*>(jb.P + idx);
-    const size_t per4 = per / 4;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    int s = 0;
-    for (; s + 8 <= nsplit; s += 8) {
-        float4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(s + u) * per4];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {           // the additions keep their order
-            acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w;
-        }
-    }
-    for (; s < nsplit; ++s) {
-        const float4 v = p[(size_t)s * per4];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    float* d = jb.dw + ((size_t)n * K + k) * taps + t;
-    if (taps == 1) {
-        *reinterpret_cast<float4*>(d) = acc;
-    } else {
-        d[0] = acc.x; d[taps] = acc.y; d[2 * taps] = acc.z; d[3 * taps] = acc.w;
-    }
+    wgrad_reduce_body(jb.P, jb.dw, jb.N, jb.K, jb.taps, jb.nsplit, idx4 - jb.f4_begin);
 }
 
 static int wgrad_nsplit(long long M, int tiles, int taps)
@@ -460,14 +436,53 @@ static int wgrad_nsplit(long long M, int tiles, int taps)
     return (int)s;
 }
 
+// pixels per range: M over nsplit ranges, rounded up to whole k-steps (the last range may be shorter, or ragged)
+static int wgrad_m_per_split(long long M, long long nsplit)
+{
+    return (int)(((M + nsplit - 1) / nsplit + WG_ROWS - 1) / WG_ROWS) * WG_ROWS;
+}
+
+// bytes of the partials [nsplit][Cout][taps][Cin] of one job
+static size_t wgrad_partial_bytes(long long nsplit, int Cin, int Cout, int taps)
+{
+    return (size_t)nsplit * Cout * taps * Cin * sizeof(float);
+}
+
+// (256 n) x (256 k) x tap tiles of dW; 0: channel counts or taps the kernel does not tile
+static int wgrad_tiles(int Cin, int Cout, int taps)
+{
+    if (Cin <= 0 || Cout <= 0 || Cin % 256 != 0 || Cout % 256 != 0 || (taps != 1 && taps != 9)) return 0;
+    return (Cout / 256) * (Cin / 256) * taps;
+}
+
+// THE shape rules of a weight-gradient job, for the single launch and for every job of a grouped one (the pointers of q are
+// the caller's business: the two entries test them at different points).  Fills M, N, K, taps, s1 and geo of j and the
+// tile count.  The codes and the order of the checks are pinned by tests/test_wgrad_host.py.
+static int wgrad_job_check(const hiast_wgrad_job& q, WJob& j, int& tiles)
+{
+    if (q.B <= 0 || q.H <= 0 || q.W <= 0 || q.stride <= 0 || q.dil <= 0) return HIAST_E_ARG;
+    tiles = wgrad_tiles(q.Cin, q.Cout, q.taps);
+    if (tiles == 0 || (q.taps == 1 && q.stride != 1)) return HIAST_E_RANGE;
+    const int Ho = q.taps == 1 ? q.H : (q.H - 1) / q.stride + 1, Wo = q.taps == 1 ? q.W : (q.W - 1) / q.stride + 1;
+    const long long M = (long long)q.B * Ho * Wo;
+    if ((size_t)M * q.Cout * 2 >= (1ull << 31) || (size_t)q.B * q.H * q.W * q.Cin * 2 >= (1ull << 31) || M >= (1ll << 24))
+        return HIAST_E_RANGE;
+    // 3x3: the pixel walk moves 4 columns with one row wrap; its linear pixel index feeds a 24-bit multiply
+    if (q.taps == 9 && (Wo < 4 || (long long)q.B * q.H * q.W + 64 >= (1ll << 23))) return HIAST_E_RANGE;
+    j.M = (int)M; j.N = q.Cout; j.K = q.Cin; j.taps = q.taps;
+    j.s1 = (q.taps == 9 && q.stride == 1 && Wo >= 20) ? 1 : 0;
+    j.geo = {q.H, q.W, Ho, Wo, q.stride, q.dil};
+    return 0;
+}
+
 }  // namespace hiast
 
+// (knows the OUTPUT map only: of the job's rules, the ones on channels and taps)
 extern "C" size_t hiast_conv_wgrad_workspace_bytes(int B, int Ho, int Wo, int Cin, int Cout, int taps)
 {
-    if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin % 256 != 0 || Cout % 256 != 0 || (taps != 1 && taps != 9)) return 0;
-    const long long M = (long long)B * Ho * Wo;
-    const int tiles = (Cout / 256) * (Cin / 256) * taps;
-    return (size_t)hiast::wgrad_nsplit(M, tiles, taps) * Cout * taps * Cin * sizeof(float);
+    const int tiles = hiast::wgrad_tiles(Cin, Cout, taps);
+    if (B <= 0 || Ho <= 0 || Wo <= 0 || tiles == 0) return 0;
+    return hiast::wgrad_partial_bytes(hiast::wgrad_nsplit((long long)B * Ho * Wo, tiles, taps), Cin, Cout, taps);
 }
 
 extern "C" int hiast_conv_wgrad_nhwc(const void* dy, const void* x, float* dw, int B, int H, int W, int Cin, int Cout,
@@ -477,29 +492,22 @@ extern "C" int hiast_conv_wgrad_nhwc(const void* dy, const void* x, float* dw, i
     if (fmt != HIAST_FMT_BF16 && fmt != HIAST_FMT_FP16) return HIAST_E_RANGE;
     const bool f16 = fmt == HIAST_FMT_FP16;
     if (!dy || !x || !dw || !workspace) return HIAST_E_ARG;
-    if (B <= 0 || H <= 0 || W <= 0 || stride <= 0 || dil <= 0) return HIAST_E_ARG;
-    if (Cin % 256 != 0 || Cout % 256 != 0 || (taps != 1 && taps != 9) || (taps == 1 && stride != 1)) return HIAST_E_RANGE;
+    const hiast_wgrad_job q = {dy, x, dw, B, H, W, Cin, Cout, taps, stride, dil};
+    hiast::WJob j;
+    int tiles = 0;
+    const int e = hiast::wgrad_job_check(q, j, tiles);
+    if (e) return e;
     if ((((uintptr_t)dy) | ((uintptr_t)x) | ((uintptr_t)dw) | ((uintptr_t)workspace)) & 15) return HIAST_E_RANGE;
-    const int Ho = taps == 1 ? H : (H - 1) / stride + 1, Wo = taps == 1 ? W : (W - 1) / stride + 1;
-    const long long M = (long long)B * Ho * Wo;
-    if ((size_t)M * Cout * 2 >= (1ull << 31) || (size_t)B * H * W * Cin * 2 >= (1ull << 31) || M >= (1ll << 24))
-        return HIAST_E_RANGE;
-    // 3x3: the pixel walk moves 4 columns with one row wrap; its linear pixel index feeds a 24-bit multiply
-    if (taps == 9 && (Wo < 4 || (long long)B * H * W + 64 >= (1ll << 23))) return HIAST_E_RANGE;
-    const int tiles = (Cout / 256) * (Cin / 256) * taps;
-    const int nsplit = hiast::wgrad_nsplit(M, tiles, taps);
-    if (workspace_bytes < (size_t)nsplit * Cout * taps * Cin * sizeof(float)) return HIAST_E_WS;
-    int mps = (int)((M + nsplit - 1) / nsplit);
-    mps = ((mps + hiast::WG_ROWS - 1) / hiast::WG_ROWS) * hiast::WG_ROWS;
-    hiast::WGeo geo = {H, W, Ho, Wo, stride, dil};
+    const int nsplit = hiast::wgrad_nsplit(j.M, tiles, taps);
+    if (workspace_bytes < hiast::wgrad_partial_bytes(nsplit, Cin, Cout, taps)) return HIAST_E_WS;
+    const int mps = hiast::wgrad_m_per_split(j.M, nsplit);
     hipStream_t st = (hipStream_t)stream;
     dim3 grid(tiles, nsplit);
 #define WL(T, F, S)                                                                                             \
     hipLaunchKernelGGL((hiast::wgrad_tn_kernel<T, F, S>), grid, dim3(512), 0, st, (const unsigned short*)dy,     \
-                       (const unsigned short*)x, (float*)workspace, (int)M, Cout, Cin, geo, mps)
-    const bool s1 = stride == 1 && Wo >= 20;
+                       (const unsigned short*)x, (float*)workspace, j.M, Cout, Cin, j.geo, mps)
     if (taps == 1) { if (f16) WL(1, true, false); else WL(1, false, false); }
-    else if (s1) { if (f16) WL(9, true, true); else WL(9, false, true); }
+    else if (j.s1) { if (f16) WL(9, true, true); else WL(9, false, true); }
     else { if (f16) WL(9, true, false); else WL(9, false, false); }
 #undef WL
     HIAST_CHECK_LAUNCH();
@@ -519,29 +527,19 @@ static int wgrad_group_plan(const hiast_wgrad_job* jobs, int njobs, hiast::WGrou
     long long f4 = 0, mmin = -1;
     for (int i = 0; i < njobs; ++i) {
         const hiast_wgrad_job& q = jobs[i];
-        if (q.B <= 0 || q.H <= 0 || q.W <= 0 || q.stride <= 0 || q.dil <= 0) return HIAST_E_ARG;
-        if (q.Cin % 256 != 0 || q.Cout % 256 != 0 || (q.taps != 1 && q.taps != 9) || (q.taps == 1 && q.stride != 1))
-            return HIAST_E_RANGE;
-        const int Ho = q.taps == 1 ? q.H : (q.H - 1) / q.stride + 1, Wo = q.taps == 1 ? q.W : (q.W - 1) / q.stride + 1;
-        const long long M = (long long)q.B * Ho * Wo;
-        if ((size_t)M * q.Cout * 2 >= (1ull << 31) || (size_t)q.B * q.H * q.W * q.Cin * 2 >= (1ull << 31) || M >= (1ll << 24))
-            return HIAST_E_RANGE;
-        if (q.taps == 9 && (Wo < 4 || (long long)q.B * q.H * q.W + 64 >= (1ll << 23))) return HIAST_E_RANGE;
         hiast::WJob& j = g.j[i];
+        const int e = hiast::wgrad_job_check(q, j, tiles_of[i]);
+        if (e) return e;
         j.dY = (const unsigned short*)q.dy;
         j.X = (const unsigned short*)q.x;
         j.dw = q.dw;
-        j.M = (int)M; j.N = q.Cout; j.K = q.Cin; j.taps = q.taps;
-        j.s1 = (q.taps == 9 && q.stride == 1 && Wo >= 20) ? 1 : 0;
-        j.geo = {q.H, q.W, Ho, Wo, q.stride, q.dil};
         j.f4_begin = (int)f4;
-        tiles_of[i] = (q.Cout / 256) * (q.Cin / 256) * q.taps;
         if (tiles_of[i] > 64) return HIAST_E_RANGE;          // (6 bits of the block map)
         tiles += tiles_of[i];
         (q.taps == 1 ? tiles1 : tiles9) += tiles_of[i];
         f4 += (long long)q.Cout * q.Cin * q.taps / 4;
         if (f4 >= (1ll << 31)) return HIAST_E_RANGE;
-        mmin = (mmin < 0 || M < mmin) ? M : mmin;
+        mmin = (mmin < 0 || j.M < mmin) ? j.M : mmin;
     }
     if (tiles > hiast::WG_MAXBLOCKS || tiles > hiast_grid_cus()) return HIAST_E_RANGE;
     // ONE round of <= 256 blocks (see wgrad_nsplit), at least 16 k-steps per block.  Uniform split first; when the launch
@@ -576,10 +574,9 @@ static int wgrad_group_plan(const hiast_wgrad_job* jobs, int njobs, hiast::WGrou
         hiast::WJob& j = g.j[i];
         const long long ns = j.taps == 1 ? s1 : s9;
         j.nsplit = (int)ns;
-        int mps = (int)((j.M + ns - 1) / ns);
-        j.m_per_split = ((mps + hiast::WG_ROWS - 1) / hiast::WG_ROWS) * hiast::WG_ROWS;
+        j.m_per_split = hiast::wgrad_m_per_split(j.M, ns);
         j.P = (float*)off;                               // offset for now; the launch adds the workspace base
-        off += (size_t)ns * j.N * j.taps * j.K * sizeof(float);
+        off += hiast::wgrad_partial_bytes(ns, j.K, j.N, j.taps);
         for (int sp = 0; sp < (int)ns; ++sp)
             for (int t = 0; t < tiles_of[i]; ++t) {
                 if (nblocks >= hiast::WG_MAXBLOCKS) return HIAST_E_RANGE;

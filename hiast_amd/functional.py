@@ -595,15 +595,13 @@ class _ConvNhwcFn(torch.autograd.Function):
                                     False, 1, dil).permute(0, 3, 1, 2)
         if ctx.shared is not None and ctx.gives:
             dx = ctx.shared.give(dx)           # the downsample convolution's backward (it runs after this one) adds it
-        own_w = need_w and not SW.on("HIAST_LIB_WGRAD") and K.conv_wgrad_preferred(
-            weight.shape[1], weight.shape[0], k, stride) and (k == 1 or dy.shape[3] >= 4)
-        small_w = need_w and not own_w and not SW.on("HIAST_LIB_WGRAD") and K.conv_wgrad_small_supported(
-            weight.shape[1], weight.shape[0], k, stride)
+        path_w = wgrad_path(weight.shape[1], weight.shape[0], k, stride, dy.shape[3]) if need_w else None
+        own_w, small_w = path_w == "own", path_w == "small"
         # The weight gradient is off the critical path of the backward pass (nothing but the optimiser consumes it)
         # and MFMA-bound, while the BatchNorm backward passes that follow on the main stream are HBM-bound: in a
         # single-process run it goes to a side stream and co-runs with them (wgrad_stream_join() before the optimiser
         # step).  Under DDP the reducer reads gradients as soon as autograd delivers them, so it stays on the main stream.
-        if need_w and own_w and ctx.wgroup is not None:
+        if own_w and ctx.wgroup is not None:
             # grouped weight gradient (hiast_conv_wgrad_group_nhwc): hand the operands to the bottleneck's _WGroupFn node,
             # whose backward runs when the last of the block's convolutions has delivered its pair, and return a
             # zero-stride placeholder of the weight's shape (no memory, no kernel) for autograd to pass on to it
@@ -634,6 +632,17 @@ class _ConvNhwcFn(torch.autograd.Function):
                                                                 # (DDP compares strides with its bucket view literally)
             made.append(dw)
         return dx, dw
+
+
+def wgrad_path(Cin, Cout, k, stride, Wo):
+    """which weight-gradient path the backward of a Cin -> Cout k x k convolution with an output map Wo columns wide takes:
+    "own" (hiast_conv_wgrad_nhwc, alone or as a job of a grouped launch), "small" (hiast_conv_wgrad_small_nhwc) or "lib" (ATen)"""
+    if SW.on("HIAST_LIB_WGRAD"):
+        return "lib"
+    # Wo >= 4: the rule of hiast_conv_wgrad_nhwc for its 3x3 form (wgrad_job_check: the pixel walk moves 4 columns with one row wrap)
+    if K.conv_wgrad_preferred(Cin, Cout, k, stride) and (k == 1 or Wo >= 4):
+        return "own"
+    return "small" if K.conv_wgrad_small_supported(Cin, Cout, k, stride) else "lib"
 
 
 _wgrad_tokens = {}
@@ -685,13 +694,11 @@ def wgroup_weights(convs, x):
     weight view) for the members of ONE grouped weight-gradient launch on the training path of x, None for the others (all of
     them when no group pays)"""
     out = [None] * len(convs)
-    if (len(convs) < 2 or len(convs) > 4 or SW.on("HIAST_NO_WGROUP")
-            or SW.on("HIAST_LIB_WGRAD") or not torch.is_grad_enabled()):
+    if len(convs) < 2 or len(convs) > 4 or SW.on("HIAST_NO_WGROUP") or not torch.is_grad_enabled():
         return out
-    for c in convs:
-        k = c.kernel_size[0]
+    for c in convs:     # every member an own-kernel shape (stride 1: every map of the block is as wide as x)
         if (not c.weight.requires_grad or not conv_nhwc_ok(x, c) or c.stride[0] != 1
-                or not K.conv_wgrad_preferred(c.in_channels, c.out_channels, k, 1)):
+                or wgrad_path(c.in_channels, c.out_channels, c.kernel_size[0], 1, x.shape[3]) != "own"):
             return out
     # A grouped launch is ONE round of (tiles x pixel ranges) <= 256 blocks: worth it when that fills the chip.  layer3:
     # 4 + 9 + 4 tiles x 15 ranges = 255 blocks (190 us against 239 us one by one); layer4: 16 + 36 + 16 tiles x 3 ranges

@@ -1445,9 +1445,6 @@ def stem_train_fwd(x, weight, fmt):
     return y, partial
 
 
-_stem_ws = {}
-
-
 def stem_wgrad(x, dy):
     """K9k: dW fp32 [64,3,7,7] of the stem convolution from x fp32 [B,3,H,W] (NCHW) and dy [B,Hc,Wc,64] 16-bit rows"""
     _req(x, torch.float32, 4, "x")
@@ -1458,11 +1455,7 @@ def stem_wgrad(x, dy):
     need = lib.hiast_stem_wgrad_workspace_bytes(B, H, W)
     if need == 0:
         raise _lib.HiastLibraryError("hiast_stem_wgrad: unsupported geometry B=%d H=%d W=%d" % (B, H, W))
-    key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _stem_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
-        _stem_ws[key] = ws
+    ws = _stream_workspace("stem", x.device, need)
     dw = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x.device)
     check(lib.hiast_stem_wgrad(_ptr(x), _ptr(dy), _ptr(dw), fmt_of(dy), B, H, W, _ptr(ws), ws.numel() * 4, _stream()),
           "hiast_stem_wgrad")
@@ -1818,6 +1811,28 @@ def bn_nhwc_bwd_apply(dy, y, x, gamma, beta, save_mean, save_invstd, sums, count
 _wgrad_ws = {}
 
 
+def _stream_workspace(kind, device, nbytes):
+    """-> fp32 scratch of at least nbytes: one growing buffer per (kind, device, stream).  Launches of ONE stream reuse it in
+    stream order; the weight gradients of a backward pass run on two streams (main for the layers whose data gradient is
+    the library's, the side stream for the rest) and two launches that shared the partials would overwrite each other's"""
+    key = (kind, device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _wgrad_ws.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _wgrad_ws[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def _wgrad_pair(dy, x, k, stride):
+    """the operand checks of one weight-gradient job: dy [B,Ho,Wo,Cout], x [B,H,W,Cin] 16-bit channels-last rows of one
+    type, Ho x Wo the output map of a k x k convolution of that stride ('same' padding) -> (B, H, W, Cin, Ho, Wo, Cout)"""
+    _req16(dy, 4, "dy")
+    _req(x, dy.dtype, 4, "x")
+    B, H, W, Cin = x.shape
+    Bo, Ho, Wo, Cout = dy.shape
+    assert Bo == B and (Ho, Wo) == ((H, W) if k == 1 else ((H - 1) // stride + 1, (W - 1) // stride + 1))
+    return B, H, W, Cin, Ho, Wo, Cout
+
+
 def conv_wgrad_supported(Cin, Cout, k, stride):
     """shapes hiast_conv_wgrad_nhwc accepts"""
     return Cin % 256 == 0 and Cout % 256 == 0 and k in (1, 3) and (k == 3 or stride == 1)
@@ -1849,27 +1864,16 @@ def conv_wgrad_small_supported(Cin, Cout, k, stride):
 
 def conv_wgrad_small_nhwc(dy, x, k, stride, dil):
     """dy [B,Ho,Wo,Cout], x [B,H,W,Cin] bf16 / fp16 channels-last rows -> dW fp32 [Cout,Cin,k,k] (K9h)"""
-    _req16(dy, 4, "dy")
-    _req(x, dy.dtype, 4, "x")
     if stride != 1 and k == 1:
         x = x[:, ::stride, ::stride, :].contiguous()         # a strided 1x1 sees every stride-th pixel only
         stride = 1
-    B, H, W, Cin = x.shape
-    Bo, Ho, Wo, Cout = dy.shape
-    assert (Bo, Ho, Wo) == (B, (H - 1) // stride + 1, (W - 1) // stride + 1)
+    B, H, W, Cin, Ho, Wo, Cout = _wgrad_pair(dy, x, k, stride)
     taps = k * k
     lib = _lib.load()
     n = lib.hiast_conv_wgrad_small_workspace_bytes(B, Ho, Wo, Cin, Cout, taps)
     if n == 0:
         raise _lib.HiastLibraryError("hiast_conv_wgrad_small_nhwc: unsupported shape Cin=%d Cout=%d taps=%d" % (Cin, Cout, taps))
-    # one growing scratch buffer per (device, stream): launches of ONE stream reuse it in stream order; the weight gradients
-    # of a backward pass run on two streams (main for the layers whose data gradient is the library's, the side stream for
-    # the rest) and two launches that shared the partials would overwrite each other's
-    key = ("small", x.device, torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() * 4 < n:
-        ws = torch.empty((n + 3) // 4, dtype=torch.float32, device=x.device)
-        _wgrad_ws[key] = ws
+    ws = _stream_workspace("small", x.device, n)
     dw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
     check(lib.hiast_conv_wgrad_small_nhwc(_ptr(dy), _ptr(x), _ptr(dw), B, H, W, Cin, Cout, taps, int(stride), int(dil), fmt_of(dy),
                                           _ptr(ws), ws.numel() * 4, _stream()), "hiast_conv_wgrad_small_nhwc")
@@ -1878,21 +1882,13 @@ def conv_wgrad_small_nhwc(dy, x, k, stride, dil):
 
 def conv_wgrad_nhwc(dy, x, k, stride, dil):
     """dy [B,Ho,Wo,Cout], x [B,H,W,Cin] bf16 / fp16 channels-last rows (same type) -> dW fp32 [Cout,Cin,k,k]"""
-    _req16(dy, 4, "dy")
-    _req(x, dy.dtype, 4, "x")
-    B, H, W, Cin = x.shape
-    Bo, Ho, Wo, Cout = dy.shape
+    B, H, W, Cin, Ho, Wo, Cout = _wgrad_pair(dy, x, k, stride)
     taps = k * k
-    assert Bo == B and (Ho, Wo) == ((H, W) if k == 1 else ((H - 1) // stride + 1, (W - 1) // stride + 1))
     lib = _lib.load()
     n = lib.hiast_conv_wgrad_workspace_bytes(B, Ho, Wo, Cin, Cout, taps)
     if n == 0:
         raise _lib.HiastLibraryError("hiast_conv_wgrad_nhwc: unsupported shape Cin=%d Cout=%d taps=%d" % (Cin, Cout, taps))
-    key = ("big", x.device, torch.cuda.current_stream(x.device).cuda_stream)     # per stream: see conv_wgrad_small_nhwc
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() * 4 < n:
-        ws = torch.empty((n + 3) // 4, dtype=torch.float32, device=x.device)
-        _wgrad_ws[key] = ws
+    ws = _stream_workspace("big", x.device, n)
     dw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
     check(lib.hiast_conv_wgrad_nhwc(_ptr(dy), _ptr(x), _ptr(dw), B, H, W, Cin, Cout, taps, int(stride), int(dil), fmt_of(dy),
                                     _ptr(ws), ws.numel() * 4, _stream()), "hiast_conv_wgrad_nhwc")
@@ -1911,11 +1907,7 @@ def conv_wgrad_group(jobs):
     outs = []
     fmt = None
     for i, (dy, x, k, stride, dil) in enumerate(jobs):
-        _req16(dy, 4, "dy")
-        _req(x, dy.dtype, 4, "x")
-        B, H, W, Cin = x.shape
-        Bo, Ho, Wo, Cout = dy.shape
-        assert Bo == B and (Ho, Wo) == ((H, W) if k == 1 else ((H - 1) // stride + 1, (W - 1) // stride + 1))
+        B, H, W, Cin, _, _, Cout = _wgrad_pair(dy, x, k, stride)
         assert fmt is None or fmt == fmt_of(dy), "one operand type per grouped launch"
         fmt = fmt_of(dy)
         dw = torch.empty((Cout, Cin, k, k), dtype=torch.float32, device=x.device)
@@ -1925,12 +1917,7 @@ def conv_wgrad_group(jobs):
     if need == 0:
         raise _lib.HiastLibraryError("hiast_conv_wgrad_group_nhwc: unsupported shapes %s" %
                                      [(tuple(j[0].shape), tuple(j[1].shape), j[2]) for j in jobs])
-    dev = jobs[0][1].device
-    key = ("group", dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
-        _wgrad_ws[key] = ws
+    ws = _stream_workspace("group", jobs[0][1].device, need)
     check(lib.hiast_conv_wgrad_group_nhwc(ctypes.addressof(arr), n, fmt, _ptr(ws), ws.numel() * 4, _stream()),
           "hiast_conv_wgrad_group_nhwc")
     return outs
@@ -1947,12 +1934,7 @@ def _disc_conv_ws(x_shape, Cout, device):
     n = disc_conv_workspace_bytes(B, Cin, Cout, H, W)
     if n == 0:
         raise _lib.HiastLibraryError("hiast_disc_conv: unsupported shape x=%s Cout=%d" % (tuple(x_shape), Cout))
-    key = ("disc", device, torch.cuda.current_stream(device).cuda_stream)      # per stream: see conv_wgrad_small_nhwc
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() * 4 < n:
-        ws = torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
-        _wgrad_ws[key] = ws
-    return ws
+    return _stream_workspace("disc", device, n)
 
 
 def _disc_conv_shapes(x, weight):

@@ -3,6 +3,7 @@
 batches, EMA teacher on the weak view (no grad, eval), student on the strong view, 4-term loss, EMA
 update every `iter_update` iterations.  Teacher and student both hand over LOW-RES logits; the teacher's
 softmax (its arg-max for cst_loss.type 'CE', reference :113-124) happens inside the fused loss kernel."""
+import gc
 import os
 
 import numpy as np
@@ -83,6 +84,11 @@ class GraphedTrainStep:
             for plan in self._plans():
                 plan.versions = None              # the re-pack launches must be IN the graph whatever moved last
             tr.g_optimizer.zero_grad(set_to_none=True)        # the graph's backward allocates the (from now on static) gradients
+            # torch.cuda.graph no longer collects garbage before a capture (torch.compiler.config.force_cudagraph_gc).  A trainer
+            # is a reference cycle with its GraphedTrainStep: a dropped one keeps its graph and pool until the cyclic collector
+            # runs, and when that happened INSIDE this capture (second trainer of one process) the process aborted in the
+            # collector.  Collect now: what is garbage is destroyed before the capture begins.
+            gc.collect()
             torch.cuda.synchronize()
             # (no torch.cuda.empty_cache() here: round 6 tried it — hand the warm-up's blocks back before the graph allocates its
             # private pool — and the full GPU suite then died with a segmentation fault inside hipGraphLaunch at the replay of the

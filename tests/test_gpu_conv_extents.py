@@ -22,6 +22,7 @@ hiast_xconv_dgrad_gated_bn_stats        test_xconv_dgrad_gated_bn_stats_extents
 hiast_conv_wgrad_nhwc                   test_conv_wgrad_extents
 hiast_conv_wgrad_small_nhwc             test_conv_wgrad_small_extents
 hiast_conv_wgrad_group_nhwc             test_conv_wgrad_group_extents
+both, on small integers: EXACT dW       test_conv_wgrad_exact_on_small_integers
 hiast_stem_train_fwd, hiast_stem_wgrad  test_stem_train_extents
 size limits of all of them              test_refused_shapes_write_nothing, test_workspace_one_byte_short_is_refused
 """
@@ -555,6 +556,56 @@ def test_conv_wgrad_group_extents(K, dt):
         assert GB.finite(dw)
         _wgrad_close(dw, _wgrad_ref(x, dy, k, stride, dil), (tuple(x.shape), k))
         assert _biteq(dw, dw_w)
+
+
+# Exact weight gradients.  dy and x hold integers of {-2 .. 2} (exact in fp16 and bf16): every product and every partial sum
+# is an integer of magnitude <= 4 M <= 131072 < 2^24, exact in fp32 whatever the order of summation, so dW must EQUAL the
+# float64 gradient — a reduction that skips, repeats or misplaces a pixel range, a tap or a k cannot hide in a tolerance.
+# name: ([(B, Cin, Cout, H, W, k, dil, stride), ...], pixel ranges per job on 256 CUs)
+EXACT_WGRAD = {
+    "1x1, 11 ranges": ([(1, 256, 256, 53, 107, 1, 1, 1)], 11),         # M = 5671: one unrolled round of 8 + a tail of 3, ragged last range
+    "3x3 s1, 11 ranges": ([(1, 256, 256, 53, 107, 3, 1, 1)], 11),      # the shifted-descriptor form, tap-strided store
+    "1x1, 64 ranges": ([(1, 256, 256, 128, 256, 1, 1, 1)], 64),        # M = 32768, the cap: eight full rounds, empty tail
+    "group 1x1 + 3x3": ([(1, 512, 256, 53, 107, 1, 1, 1), (1, 256, 256, 53, 107, 3, 1, 1)], 11),   # the second job's f4_begin
+}
+_exact_cache = {}
+
+
+def _exact_wgrad_case(name):
+    """-> [(x int8 [B,H,W,Cin], dy int8 [B,Ho,Wo,Cout], float64 dW)] on the CPU, computed once for both operand types"""
+    if name not in _exact_cache:
+        gen = torch.Generator().manual_seed(9960 + sorted(EXACT_WGRAD).index(name))
+        jobs = []
+        for B, Cin, Cout, H, W, k, dil, stride in EXACT_WGRAD[name][0]:
+            x = torch.randint(-2, 3, (B, H, W, Cin), generator=gen, dtype=torch.int8)
+            dy = torch.randint(-2, 3, (B, (H - 1) // stride + 1, (W - 1) // stride + 1, Cout), generator=gen, dtype=torch.int8)
+            jobs.append((x, dy, _wgrad_ref(x, dy, k, stride, dil)))
+        _exact_cache[name] = jobs
+    return _exact_cache[name]
+
+
+@pytest.mark.parametrize("name", list(EXACT_WGRAD))
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+def test_conv_wgrad_exact_on_small_integers(K, name, dt):
+    """hiast_conv_wgrad_nhwc / hiast_conv_wgrad_group_nhwc: torch.equal against float64, at the split counts stated above"""
+    cfgs, splits = EXACT_WGRAD[name]
+    lib = K._lib.load()
+    per_split = [Cout * k * k * Cin * 4 for _, Cin, Cout, _, _, k, _, _ in cfgs]
+    if len(cfgs) == 1:
+        B, Cin, Cout, H, W, k, dil, stride = cfgs[0]
+        need = lib.hiast_conv_wgrad_workspace_bytes(B, (H - 1) // stride + 1, (W - 1) // stride + 1, Cin, Cout, k * k)
+    else:
+        arr = (K._lib.WgradJob * len(cfgs))(*[K._lib.WgradJob(None, None, None, B, H, W, Cin, Cout, k * k, stride, dil)
+                                               for B, Cin, Cout, H, W, k, dil, stride in cfgs])
+        need = lib.hiast_conv_wgrad_group_workspace_bytes(ctypes.addressof(arr), len(cfgs))
+    # (another CU count would split differently and quietly test less)
+    assert need % sum(per_split) == 0 and need // sum(per_split) == splits, (need, per_split)
+    case = _exact_wgrad_case(name)
+    jobs = [(dy.cuda().to(dt), x.cuda().to(dt), c[5], c[7], c[6]) for (x, dy, _), c in zip(case, cfgs)]      # (dy, x, k, stride, dil)
+    outs = [K.conv_wgrad_nhwc(*jobs[0])] if len(jobs) == 1 else K.conv_wgrad_group(jobs)
+    for dw, (_, _, ref), cfg in zip(outs, case, cfgs):
+        assert float(ref.abs().max()) < 2.0 ** 24
+        assert torch.equal(dw.cpu().double(), ref), (name, cfg, float((dw.cpu().double() - ref).abs().max()))
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
